@@ -13,6 +13,10 @@ batch (weak scaling, replicas only: inference has no collective -- SURVEY.md 8e)
 Other BASELINE configs through the same file: `--cfg experiments/cfgs/fpn_resnet50_640.yml --batch 32` (config 3),
 `--cfg experiments/cfgs/bifpn_regnetx008_896.yml --batch 16 --dtype fp16 --graph 1` (config 5).
 
+`--dump-outputs DIR` writes what the last timed step returned on rank 0 -- the detections a caller of the step receives
+(scores.npy, boxes.npy, classes.npy, float32) -- after the timed region.  Weights and images are seeded, so the same
+arguments give the same inputs on every run and two builds can be compared output for output.
+
 The whole step runs in line on one stream by default.  Serving-loop pipelining is an option (--tail-stream 1): the
 latency-bound end of the decode stage (levelsel_kernel + nmswalk_kernel: per-level select + box decode, NMS) is then
 enqueued on its own HIP stream and runs under the NEXT step's forward pass while the HBM-bound scan16_kernel stays in
@@ -75,7 +79,50 @@ def parse():
     ap.add_argument("--stub-cpu", type=int, default=0,
                     help="(tests/test_ddp_cpu.py) 1: exercise ONLY the launcher / rank / timing logic on CPU under gloo with a "
                          "sleeping step -- no model, no kernels, prints a line marked data='stub'; never a measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (scores, boxes, classes of rank 0) "
+                         "as DIR/<name>.npy in float32 (at most 64 MB in all: a fixed, seeded sample of images beyond that)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (the number of timed steps)")
+    return args
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, cap_bytes=DUMP_CAP_BYTES, seed=0):
+    """--dump-outputs: `arrays` (name -> tensor or array, all with the batch as the first dimension) -> out_dir/<name>.npy,
+    float64 kept, everything else as float32.  When they exceed `cap_bytes` together, every array is cut to the same fixed,
+    seeded sample of images (ascending), whose indices go to out_dir/image_index.npy.  Returns {file name: shape}."""
+    import numpy as np
+
+    host = OrderedDict()
+    for k, v in arrays.items():
+        if hasattr(v, "detach"):  # torch tensor (numpy has no bfloat16: every non-float64 dtype goes through float32)
+            v = v.detach().cpu()
+            v = v.double() if v.dtype.is_floating_point and v.element_size() == 8 else v.float()
+            v = v.numpy()
+        a = np.asarray(v)
+        host[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    rows = {a.shape[0] for a in host.values()}
+    if len(rows) != 1:
+        raise ValueError("dump_outputs: the arrays do not share a batch dimension: %s" % {k: a.shape for k, a in host.items()})
+    n = rows.pop()
+    if sum(a.nbytes for a in host.values()) > cap_bytes:
+        per_image = sum(a.nbytes // max(n, 1) for a in host.values()) + 8  # + its float64 index
+        keep = cap_bytes // per_image
+        if keep < 1:
+            raise ValueError("dump_outputs: one image's outputs (%d bytes) exceed the cap of %d bytes" % (per_image, cap_bytes))
+        idx = np.sort(np.random.RandomState(seed).choice(n, int(keep), replace=False))
+        host = OrderedDict((k, a[idx]) for k, a in host.items())
+        host["image_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    written = OrderedDict()
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+        written[k + ".npy"] = list(a.shape)
+    return written
 
 
 def timed_region(step, steps, warmup, barrier, world, reduce_max, before_timed=None):
@@ -400,6 +447,9 @@ def main():
     elapsed, out = timed_region(step, args.steps, args.warmup, barrier, world, reduce_max,
                                 before_timed=lambda: decoder.set_profiling(not args.graph))
     timed_out = [o.clone() for o in out]
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the detections of the LAST timed step, as a caller of the step receives them
+        dumped = dump_outputs(args.dump_outputs, OrderedDict(zip(("scores", "boxes", "classes"), timed_out)))
 
     # ---- per-kernel times recorded live in the timed region -------------------------------------------
     nprof = min(args.steps, 256)
@@ -622,6 +672,8 @@ def main():
         result["roofline"]["backbone_by_time"] = body
     if layers is not None and args.layers:
         result["layers"] = layers
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "of": "the last timed step, rank 0"}
 
     # ---- CPU leg (rank 0, N = 1), bounded sample of S images of the timed batch: -------------------------------------
     #   (1) checker: the numpy oracle's Decoder on the GPU's OWN head outputs of those images must reproduce the timed

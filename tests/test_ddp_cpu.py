@@ -206,6 +206,9 @@ def _main_worker(rank, world, port, cfg_path, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank), SSDK_FAST_BN="0")
     torch.set_num_threads(1)
+    # main() takes RCCL and cuda:<local_rank> whenever a device is visible: on a one-GPU machine rank 1 would ask for a
+    # second device.  This is the CPU / gloo launch on every machine, GPU or not.
+    torch.cuda.is_available = lambda: False
     from ssds.modeling.layers import box
     from ssds.utils import train_ddp
 
