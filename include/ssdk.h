@@ -562,6 +562,35 @@ int ssdk_bn_act_train_bwd(const void* x, const void* dy, const float* weight, co
                           const float* save_invstd, void* dx, float* dweight, float* dbias, void* workspace,
                           size_t workspace_bytes, int N, int C, int HW, int act, int dtype, void* stream);
 
+/* Synchronised BatchNorm: batch statistics over the local batches of all W ranks of a process group, on the passes above
+ * split at the collective.  The caller all-gathers each rank's record (fp32, planar) and hands every rank the [W][...] stack;
+ * the merges add the ranks in RANK order, so every rank computes the same bits whatever the collective does.  No call reads
+ * anything back to the host.  A rank with an empty local batch passes N = 0 (its record has count 0 and is skipped).
+ *   ssdk_bn_sync_local_stats   send [3C+1] = [s1[C] | s2[C] | pivot[C] | count]: sums of (x - pivot), (x - pivot)^2 with
+ *                              pivot = the channel's first element (0 with producer `sums` [C][2], which are only packed),
+ *                              count = N * HW as a uint32 bit pattern.  workspace: ssdk_bn_workspace_bytes(N, C).
+ *   ssdk_bn_sync_fwd_finalize  gathered [W][3C+1] -> save_mean / save_invstd, running statistics (torch semantics with the
+ *                              global count), coef [C][4] (16-byte aligned) = (a, b, 0, .) of y = act(a x + b).  Each rank's
+ *                              sums are shifted to the first non-empty rank's pivot P: s2 += 2 d s1 + n d^2, s1 += n d, d =
+ *                              pivot_r - P.  With W = 1 the results are the bits of ssdk_bn_act_train_fwd / _stats.
+ *   ssdk_bn_act_apply          y = act(a x + b) from coef (as ssdk_bn_act_train_stats / ssdk_bn_sync_fwd_finalize write it).
+ *   ssdk_bn_sync_bwd_local     send [2C] = [sum g | sum g xhat] of the local batch (g = dy masked by the activation);
+ *                              dweight / dbias (may be NULL) = these LOCAL sums (torch.nn.SyncBatchNorm's semantics).
+ *   ssdk_bn_sync_bwd_apply     gathered [W][2C] + the forward's gathered [W][3C+1] (global count) -> dx, one launch.
+ * Launches per layer: forward 3 (2 when a depthwise convolution applies coef), backward 2, each excluding the collective. */
+int ssdk_bn_sync_local_stats(const void* x, const float* sums, float* send, void* workspace, size_t workspace_bytes, int N, int C,
+                             int HW, int dtype, void* stream);
+int ssdk_bn_sync_fwd_finalize(const float* gathered, int W, const float* weight, const float* bias, float* running_mean,
+                              float* running_var, float* save_mean, float* save_invstd, float* coef, int C, float momentum,
+                              float eps, void* stream);
+int ssdk_bn_act_apply(const void* x, const float* coef, void* y, int N, int C, int HW, int act, int dtype, void* stream);
+int ssdk_bn_sync_bwd_local(const void* x, const void* dy, const float* weight, const float* bias, const float* save_mean,
+                           const float* save_invstd, float* send, float* dweight, float* dbias, void* workspace,
+                           size_t workspace_bytes, int N, int C, int HW, int act, int dtype, void* stream);
+int ssdk_bn_sync_bwd_apply(const void* x, const void* dy, const float* gathered, int W, const float* fwd_gathered,
+                           const float* weight, const float* bias, const float* save_mean, const float* save_invstd, void* dx,
+                           int N, int C, int HW, int act, int dtype, void* stream);
+
 /* ResNet stem (nets/resnet.py:41-46): 7x7 / stride 2 / pad 3 convolution on the 3-channel image + folded BN +
  * activation -> NHWC, and the 3x3 / stride 2 / pad 1 max pooling (NHWC -> NHWC, -inf padding like torch).
  *   x  image [N,3,H,W] (in_layout NCHW) or [N,H,W,3] (NHWC), activation dtype

@@ -44,6 +44,12 @@ struct BnParams {
   int act;                 // 0 none | 1 ReLU6 | 2 ReLU fused behind the normalisation
   u32* tickets;            // [C] arrival counters of the reduction's workgroups (zero between launches): the LAST workgroup of a
                            // channel does the finalize arithmetic itself and there is no finalize launch; nullptr: the launch
+  // the split (synchronised) BatchNorm -- see the section "synchronised BatchNorm" below
+  float* send;             // != nullptr: the finish writes this rank's record (fwd [3C+1], bwd [2C]) instead of finishing
+  const float* gathered;   // bwd apply: [W][2C] backward records of all ranks (the apply pass forms its coefficients itself)
+  const float* fwd_gathered;  // bwd apply: [W][3C+1] forward records (the global count)
+  int W;
+  int apply_only;          // the apply pass alone (coefficients given in `coef`, or formed from `gathered`)
 };
 
 // the activation's pass-through mask on the pre-activation value as the forward pass stored it (rounded to DT)
@@ -153,11 +159,9 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const BnParams p) {
   }
 }
 
-// forward statistics -> mean, invstd, running stats, apply coefficients (a, b) of channel c from its sums (s1, s2)
-template <int DT>
-__device__ __forceinline__ void bn_fwd_finish(const BnParams& p, int c, float s1, float s2) {
-  const float M = (float)p.N * (float)p.HW;
-  const float pivot = p.sums ? 0.f : bn_ld1<DT>(p.x, (size_t)c * p.HW);
+// forward statistics -> mean, invstd, running stats, apply coefficients (a, b) of channel c from its sums (s1, s2) of
+// (x - pivot), (x - pivot)^2 over M elements
+__device__ __forceinline__ void bn_fwd_out(const BnParams& p, int c, float M, float pivot, float s1, float s2) {
   const float m1 = s1 / M;
   const float mean = pivot + m1;
   float var = s2 / M - m1 * m1;  // biased
@@ -177,6 +181,18 @@ __device__ __forceinline__ void bn_fwd_finish(const BnParams& p, int c, float s1
   p.coef[c * 4 + 2] = 0.f;
 }
 template <int DT>
+__device__ __forceinline__ void bn_fwd_finish(const BnParams& p, int c, float s1, float s2) {
+  const float pivot = p.sums ? 0.f : bn_ld1<DT>(p.x, (size_t)c * p.HW);
+  if (p.send) {  // split path: the channel's entry of this rank's record; the merge finishes (bn_sync_fwd_finalize_kernel)
+    p.send[c] = s1;
+    p.send[p.C + c] = s2;
+    p.send[2 * p.C + c] = pivot;
+    if (c == 0) p.send[3 * p.C] = __builtin_bit_cast(float, (u32)p.N * (u32)p.HW);  // the count, exact (an integer)
+    return;
+  }
+  bn_fwd_out(p, c, (float)p.N * (float)p.HW, pivot, s1, s2);
+}
+template <int DT>
 __global__ __launch_bounds__(64) void bn_fwd_finalize_kernel(const BnParams p) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= p.C) return;
@@ -193,19 +209,29 @@ __global__ __launch_bounds__(64) void bn_fwd_finalize_kernel(const BnParams p) {
   bn_fwd_finish<DT>(p, c, s1, s2);
 }
 
-// backward sums -> dgamma, dbeta, coefficients of dx = a*dy + k1*x + k0
-__device__ __forceinline__ void bn_bwd_finish(const BnParams& p, int c, float sg, float sgx) {
-  if (p.dweight) p.dweight[c] = sgx;
-  if (p.dbias) p.dbias[c] = sg;
-  const float M = (float)p.N * (float)p.HW;
+// backward sums (over M elements) -> coefficients (a, k0, k1, forward offset) of dx = a*dy + k1*x + k0
+__device__ __forceinline__ float4 bn_bwd_coef(const BnParams& p, int c, float M, float sg, float sgx) {
   const float g = p.weight ? p.weight[c] : 1.f;
   const float invstd = p.save_invstd[c], mean = p.save_mean[c];
   const float a = g * invstd;
   const float k1 = -a * invstd * sgx / M;
-  p.coef[c * 4 + 0] = a;
-  p.coef[c * 4 + 1] = -a * sg / M - k1 * mean;  // k0
-  p.coef[c * 4 + 2] = k1;
-  p.coef[c * 4 + 3] = (p.bias ? p.bias[c] : 0.f) - mean * a;  // forward offset (activation mask of the apply pass)
+  return float4{a, -a * sg / M - k1 * mean,  // k0
+                k1, (p.bias ? p.bias[c] : 0.f) - mean * a};  // forward offset (activation mask of the apply pass)
+}
+// backward sums -> dgamma, dbeta (of the LOCAL batch: on the split path DDP averages them), coefficients
+__device__ __forceinline__ void bn_bwd_finish(const BnParams& p, int c, float sg, float sgx) {
+  if (p.dweight) p.dweight[c] = sgx;
+  if (p.dbias) p.dbias[c] = sg;
+  if (p.send) {  // split path: this rank's record; the apply pass merges the ranks' records (bn_sync_bwd_coef)
+    p.send[c] = sg;
+    p.send[p.C + c] = sgx;
+    return;
+  }
+  const float4 k = bn_bwd_coef(p, c, (float)p.N * (float)p.HW, sg, sgx);
+  p.coef[c * 4 + 0] = k.x;
+  p.coef[c * 4 + 1] = k.y;
+  p.coef[c * 4 + 2] = k.z;
+  p.coef[c * 4 + 3] = k.w;
 }
 __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const BnParams p) {
   const int c = blockIdx.x * 64 + threadIdx.x;
@@ -216,6 +242,61 @@ __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const BnParams p) {
     sgx += p.partial[((size_t)c * p.split + s) * 2 + 1];
   }
   bn_bwd_finish(p, c, sg, sgx);
+}
+
+// ---- synchronised BatchNorm: statistics over the batches of all ranks of a process group ----------------------------------
+// The passes above split at the finish.  The local reduction's finish writes the rank's RECORD (p.send) instead:
+//   forward  [s1[C] | s2[C] | pivot[C] | count]   sums of (x - pivot), (x - pivot)^2, pivot = the channel's first element
+//            (0 with producer sums), count = N * HW as a u32 bit pattern (exact: 8 ranks x 64 x 256^2 is above 2^24)
+//   backward [sum g[C] | sum g xhat[C]]           (g = dy masked by the activation; dweight / dbias are the LOCAL sums)
+// The records of all ranks are all-gathered by the caller, and both merges below add them in RANK order: every rank computes
+// the same bits whatever algorithm the collective uses.  (An all-reduce of (s1, s2, n) would need one pivot shared by all
+// ranks, which does not exist without another collective.)  Ranks with count 0 (an empty local batch) are skipped.
+// The forward merge shifts rank r's sums to the common pivot P (the first non-empty rank's), d = pivot_r - P:
+//   s2 += 2 d s1 + n d^2,  s1 += n d
+// -- the error stays bounded by |d| (a few standard deviations), not by |mean|.  With one rank d is never formed: the results
+// are the bits of the local path.
+__global__ __launch_bounds__(64) void bn_sync_fwd_finalize_kernel(const BnParams p) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= p.C) return;
+  const size_t L = 3 * (size_t)p.C + 1;
+  float P = 0.f, s1 = 0.f, s2 = 0.f;
+  unsigned long long M = 0;
+  for (int r = 0; r < p.W; ++r) {
+    const float* rec = p.gathered + (size_t)r * L;
+    const u32 n = __builtin_bit_cast(u32, rec[3 * (size_t)p.C]);
+    if (n == 0u) continue;
+    const float r1 = rec[c], r2 = rec[p.C + c], piv = rec[2 * (size_t)p.C + c];
+    if (M == 0) {
+      P = piv;
+      s1 = r1;
+      s2 = r2;
+    } else {
+      const float d = piv - P, fn = (float)n;
+      s2 += d != 0.f ? r2 + (2.f * d * r1 + fn * d * d) : r2;
+      s1 += d != 0.f ? r1 + fn * d : r1;
+    }
+    M += n;
+  }
+  if (M == 0) {  // every rank empty: no statistics (the running statistics keep their values)
+    p.save_mean[c] = p.save_invstd[c] = __builtin_nanf("");
+    p.coef[c * 4 + 0] = p.coef[c * 4 + 1] = p.coef[c * 4 + 2] = 0.f;
+    return;
+  }
+  bn_fwd_out(p, c, (float)M, P, s1, s2);
+}
+
+// the backward coefficients of channel c from the ranks' records, in rank order (formed by the apply pass: no finalize launch)
+__device__ __forceinline__ float4 bn_sync_bwd_coef(const BnParams& p, int c) {
+  const size_t L = 3 * (size_t)p.C + 1, L2 = 2 * (size_t)p.C;
+  unsigned long long M = 0;
+  for (int r = 0; r < p.W; ++r) M += __builtin_bit_cast(u32, p.fwd_gathered[(size_t)r * L + 3 * (size_t)p.C]);
+  float sg = p.gathered[c], sgx = p.gathered[p.C + c];
+  for (int r = 1; r < p.W; ++r) {
+    sg += p.gathered[(size_t)r * L2 + c];
+    sgx += p.gathered[(size_t)r * L2 + p.C + c];
+  }
+  return bn_bwd_coef(p, c, (float)M, sg, sgx);
 }
 
 // The finalize arithmetic WITHOUT its launch (round 6: 90 finalize launches of ~5 us per training step).  Every workgroup of
@@ -258,12 +339,19 @@ __device__ __forceinline__ void bn_fold_finalize(const BnParams& p, int c, int s
 }
 
 // MODE 0: out = x*a + b.  MODE 1: out = dy*a + x*k1 + k0.   grid (chunks of a plane, N*C planes)
-template <int DT, int MODE>
+// SYNC (MODE 1): the coefficients are formed from the ranks' records (bn_sync_bwd_coef), not read from p.coef
+template <int DT, int MODE, bool SYNC = false>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const BnParams p) {
   constexpr int VN = BnVec<DT>::n;
   const int plane = blockIdx.y;
   const int c = plane % p.C;
-  const float a = p.coef[c * 4 + 0], k0 = p.coef[c * 4 + 1], k1 = p.coef[c * 4 + 2], fb = p.coef[c * 4 + 3];
+  float a, k0, k1, fb;
+  if constexpr (SYNC) {
+    const float4 k = bn_sync_bwd_coef(p, c);
+    a = k.x, k0 = k.y, k1 = k.z, fb = k.w;
+  } else {
+    a = p.coef[c * 4 + 0], k0 = p.coef[c * 4 + 1], k1 = p.coef[c * 4 + 2], fb = p.coef[c * 4 + 3];
+  }
   const int act = p.act;
   auto fwd = [&](float x) {  // MODE 0
     float o = x * a + k0;
@@ -427,7 +515,7 @@ struct BnFlat {
 };
 
 // MODE 0: out = x*a + b (+ activation).  MODE 1: out = dy*a + x*k1 + k0 (dy masked by the activation).
-template <int DT, int MODE>
+template <int DT, int MODE, bool SYNC = false>
 __global__ __launch_bounds__(256) void bn_apply_flat_kernel(const BnParams p, const BnFlat f) {
   constexpr int VN = BnVec<DT>::n;
   const int act = p.act;
@@ -455,6 +543,19 @@ __global__ __launch_bounds__(256) void bn_apply_flat_kernel(const BnParams p, co
     return g * k.x + x * k.z + k.y;
   };
   const float4* coef = reinterpret_cast<const float4*>(p.coef);
+  int kc = -1;  // SYNC: the channel whose coefficients this thread formed last
+  float4 kk = float4{0.f, 0.f, 0.f, 0.f};
+  auto coefs = [&](int cc) {
+    if constexpr (SYNC) {
+      if (cc != kc) {
+        kc = cc;
+        kk = bn_sync_bwd_coef(p, cc);
+      }
+      return kk;
+    } else {
+      return coef[cc];
+    }
+  };
   const int nvec = (hi - lo) / VN;
   for (int vb = 0; vb < nvec; vb += 256 * kBnU) {
     u32x4 xr[kBnU], gr[kBnU];
@@ -480,12 +581,12 @@ __global__ __launch_bounds__(256) void bn_apply_flat_kernel(const BnParams p, co
       bn_unpack<DT>(gr[u], gv);
       const int pl = f.chunks > 1 ? 0 : bn_div_small(le, f.rcpHW);
       if (f.chunks > 1 || le + VN <= (pl + 1) * p.HW) {  // one plane: one set of coefficients
-        const float4 k = coef[channel(le)];
+        const float4 k = coefs(channel(le));
 #pragma unroll
         for (int e = 0; e < VN; ++e) o[e] = one(xv[e], gv[e], k);
       } else {  // the vector straddles planes (plane sizes that are not a multiple of the vector width)
 #pragma unroll
-        for (int e = 0; e < VN; ++e) o[e] = one(xv[e], gv[e], coef[channel(le + e)]);
+        for (int e = 0; e < VN; ++e) o[e] = one(xv[e], gv[e], coefs(channel(le + e)));
       }
       bn_store_raw<DT>(p.out, base + le, o);
     }
@@ -494,7 +595,7 @@ __global__ __launch_bounds__(256) void bn_apply_flat_kernel(const BnParams p, co
   if ((int)threadIdx.x < rest) {
     const int le = lo + nvec * VN + (int)threadIdx.x;
     const float x = bn_ld1<DT>(p.x, base + le), g = MODE == 1 ? bn_ld1<DT>(p.dy, base + le) : 0.f;
-    bn_st1<DT>(p.out, base + le, one(x, g, coef[channel(le)]));
+    bn_st1<DT>(p.out, base + le, one(x, g, coefs(channel(le))));
   }
 }
 
@@ -532,7 +633,7 @@ static u32* bn_tickets(int C) {
 template <int MODE>
 static void bn_launch(const BnParams& p0, hipStream_t st) {
   BnParams p = p0;
-  const bool has_reduce = !(MODE == 0 && p.sums);
+  const bool has_reduce = !(MODE == 0 && p.sums) && !p.apply_only;
   p.tickets = has_reduce ? bn_tickets(p.C) : nullptr;  // the reduction finalizes (no finalize launch)
   // 0: the per-plane kernels, 1: the flat kernels, 2 (default): the flat reduction always, the flat apply pass only where
   // the per-plane one cannot use vectors (plane size not a multiple of the vector width, or a misaligned tensor: there it
@@ -556,13 +657,16 @@ static void bn_launch(const BnParams& p0, hipStream_t st) {
   const dim3 agrid((unsigned)((p.HW + 256 * vn - 1) / (256 * vn)), (unsigned)NC);
 #define SSDK_BN(DT)                                                                                         \
   do {                                                                                                      \
-    if (MODE == 0 && p.sums) {                                                                              \
+    if ((MODE == 0 && p.sums) || p.apply_only) {                                                            \
     } else if (flat_r) hipLaunchKernelGGL((bn_reduce_flat_kernel<DT, MODE>), rgrid, dim3(256), 0, st, p);   \
     else hipLaunchKernelGGL((bn_reduce_kernel<DT, MODE>), rgrid, dim3(256), 0, st, p);                      \
-    if (p.tickets) {                                                                                        \
+    if (p.tickets || p.apply_only) {                                                                        \
     } else if (MODE == 0) hipLaunchKernelGGL((bn_fwd_finalize_kernel<DT>), dim3((unsigned)((p.C + 63) / 64)), dim3(64), 0, st, p); \
     else hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((p.C + 63) / 64)), dim3(64), 0, st, p);  \
-    if (MODE == 0 && p.no_apply) {                                                                           \
+    if (p.no_apply) {                                                                                        \
+    } else if (MODE == 1 && p.gathered) {                                                                    \
+      if (flat && fgrid < (1l << 31)) hipLaunchKernelGGL((bn_apply_flat_kernel<DT, MODE, MODE == 1>), dim3((unsigned)fgrid), dim3(256), 0, st, p, f); \
+      else hipLaunchKernelGGL((bn_apply_kernel<DT, MODE, MODE == 1>), agrid, dim3(256), 0, st, p);           \
     } else if (flat && fgrid < (1l << 31)) hipLaunchKernelGGL((bn_apply_flat_kernel<DT, MODE>), dim3((unsigned)fgrid), dim3(256), 0, st, p, f); \
     else hipLaunchKernelGGL((bn_apply_kernel<DT, MODE>), agrid, dim3(256), 0, st, p);                        \
   } while (0)
@@ -581,13 +685,9 @@ extern "C" size_t ssdk_bn_workspace_bytes(int N, int C) {
   return ((((size_t)C * bn_split(N, C) * 2 + 3) & ~(size_t)3) + (size_t)C * 4) * sizeof(float);
 }
 
-static int bn_common(BnParams& p, const char* what, int N, int C, int HW, int dtype, void* workspace, size_t workspace_bytes) {
+static int bn_shape(BnParams& p, const char* what, int N, int C, int HW, int dtype) {
   if (N < 1 || C < 1 || HW < 1 || (dtype != SSDK_F32 && dtype != SSDK_BF16 && dtype != SSDK_F16) || (long)N * C > 2147483647l) {
     set_error("%s: bad arguments N=%d C=%d HW=%d dtype=%d", what, N, C, HW, dtype);
-    return SSDK_E_BADARG;
-  }
-  if (!workspace || workspace_bytes < ssdk_bn_workspace_bytes(N, C) || ((uintptr_t)workspace & 15)) {
-    set_error("%s: workspace too small or misaligned", what);
     return SSDK_E_BADARG;
   }
   p.N = N;
@@ -595,6 +695,16 @@ static int bn_common(BnParams& p, const char* what, int N, int C, int HW, int dt
   p.HW = HW;
   p.dtype = dtype;
   p.split = bn_split(N, C);
+  return SSDK_OK;
+}
+
+static int bn_common(BnParams& p, const char* what, int N, int C, int HW, int dtype, void* workspace, size_t workspace_bytes) {
+  const int rc = bn_shape(p, what, N, C, HW, dtype);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < ssdk_bn_workspace_bytes(N, C) || ((uintptr_t)workspace & 15)) {
+    set_error("%s: workspace too small or misaligned", what);
+    return SSDK_E_BADARG;
+  }
   p.partial = (float*)workspace;
   p.coef = p.partial + (((size_t)C * p.split * 2 + 3) & ~(size_t)3);
   return SSDK_OK;
@@ -741,4 +851,175 @@ extern "C" int ssdk_bn_train_bwd(const void* x, const void* dy, const float* wei
                                  size_t workspace_bytes, int N, int C, int HW, int dtype, void* stream) {
   return ssdk_bn_act_train_bwd(x, dy, weight, nullptr, save_mean, save_invstd, dx, dweight, dbias, workspace,
                                workspace_bytes, N, C, HW, 0, dtype, stream);
+}
+
+// ---- synchronised BatchNorm (version 244, additive): the passes above split at the collective ------------------------------
+// forward:  ssdk_bn_sync_local_stats -> all-gather of the records -> ssdk_bn_sync_fwd_finalize -> ssdk_bn_act_apply (or the
+//           depthwise kernels apply coef on load: a deferred BatchNorm)
+// backward: ssdk_bn_sync_bwd_local -> all-gather of the records -> ssdk_bn_sync_bwd_apply
+// One launch each (the local reductions finalize in their last workgroup); nothing reads back to the host.  A rank whose local
+// batch is empty (N = 0) sends a record of zeros with count 0.
+static int bn_sync_check(const char* what, int N, int C, int HW, int dtype) {
+  if (N < 0 || C < 1 || HW < 1 || (dtype != SSDK_F32 && dtype != SSDK_BF16 && dtype != SSDK_F16) ||
+      (unsigned long long)N * (unsigned long long)HW > 0xffffffffull) {
+    set_error("%s: bad arguments N=%d C=%d HW=%d dtype=%d", what, N, C, HW, dtype);
+    return SSDK_E_BADARG;
+  }
+  return SSDK_OK;
+}
+
+extern "C" int ssdk_bn_sync_local_stats(const void* x, const float* sums, float* send, void* workspace, size_t workspace_bytes,
+                                        int N, int C, int HW, int dtype, void* stream) {
+  int rc = bn_sync_check("bn_sync_local_stats", N, C, HW, dtype);
+  if (rc) return rc;
+  if (!send || (N > 0 && !x)) {
+    set_error("bn_sync_local_stats: null pointer");
+    return SSDK_E_BADARG;
+  }
+  if (N == 0) {
+    if (hipMemsetAsync(send, 0, (3 * (size_t)C + 1) * sizeof(float), (hipStream_t)stream) != hipSuccess) return check_launch("bn_sync_local_stats");
+    return SSDK_OK;
+  }
+  BnParams p;
+  memset(&p, 0, sizeof(p));
+  rc = bn_common(p, "bn_sync_local_stats", N, C, HW, dtype, workspace, workspace_bytes);
+  if (rc) return rc;
+  p.x = x;
+  p.dy = x;
+  p.sums = sums;  // the producer's raw sums: the launch only packs them (pivot 0)
+  p.no_apply = 1;
+  p.send = send;
+  bn_launch<0>(p, (hipStream_t)stream);
+  return check_launch("bn_sync_local_stats");
+}
+
+extern "C" int ssdk_bn_sync_fwd_finalize(const float* gathered, int W, const float* weight, const float* bias, float* running_mean,
+                                         float* running_var, float* save_mean, float* save_invstd, float* coef, int C,
+                                         float momentum, float eps, void* stream) {
+  if (W < 1 || C < 1) {
+    set_error("bn_sync_fwd_finalize: bad arguments W=%d C=%d", W, C);
+    return SSDK_E_BADARG;
+  }
+  if (!gathered || !save_mean || !save_invstd || !coef || ((uintptr_t)coef & 15) || (!running_mean) != (!running_var)) {
+    set_error("bn_sync_fwd_finalize: null / misaligned pointer");
+    return SSDK_E_BADARG;
+  }
+  BnParams p;
+  memset(&p, 0, sizeof(p));
+  p.gathered = gathered;
+  p.W = W;
+  p.C = C;
+  p.weight = weight;
+  p.bias = bias;
+  p.running_mean = running_mean;
+  p.running_var = running_var;
+  p.save_mean = save_mean;
+  p.save_invstd = save_invstd;
+  p.coef = coef;
+  p.momentum = momentum;
+  p.eps = eps;
+  hipLaunchKernelGGL(bn_sync_fwd_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p);
+  return check_launch("bn_sync_fwd_finalize");
+}
+
+// the forward apply pass alone: y = act(a x + b) with coef [C][4] = (a, b, ., .) as ssdk_bn_act_train_stats /
+// ssdk_bn_sync_fwd_finalize write it
+extern "C" int ssdk_bn_act_apply(const void* x, const float* coef, void* y, int N, int C, int HW, int act, int dtype, void* stream) {
+  int rc = bn_sync_check("bn_act_apply", N, C, HW, dtype);
+  if (rc) return rc;
+  if (act < 0 || act > 2) {
+    set_error("bn_act_apply: act must be 0 (none), 1 (ReLU6) or 2 (ReLU)");
+    return SSDK_E_BADARG;
+  }
+  if (!coef || ((uintptr_t)coef & 15) || (N > 0 && (!x || !y))) {
+    set_error("bn_act_apply: null / misaligned pointer");
+    return SSDK_E_BADARG;
+  }
+  if (N == 0) return SSDK_OK;
+  BnParams p;
+  memset(&p, 0, sizeof(p));
+  rc = bn_shape(p, "bn_act_apply", N, C, HW, dtype);
+  if (rc) return rc;
+  p.x = x;
+  p.dy = x;
+  p.out = y;
+  p.coef = const_cast<float*>(coef);
+  p.act = act;
+  p.apply_only = 1;
+  bn_launch<0>(p, (hipStream_t)stream);
+  return check_launch("bn_act_apply");
+}
+
+extern "C" int ssdk_bn_sync_bwd_local(const void* x, const void* dy, const float* weight, const float* bias, const float* save_mean,
+                                      const float* save_invstd, float* send, float* dweight, float* dbias, void* workspace,
+                                      size_t workspace_bytes, int N, int C, int HW, int act, int dtype, void* stream) {
+  int rc = bn_sync_check("bn_sync_bwd_local", N, C, HW, dtype);
+  if (rc) return rc;
+  if (act < 0 || act > 2) {
+    set_error("bn_sync_bwd_local: act must be 0 (none), 1 (ReLU6) or 2 (ReLU)");
+    return SSDK_E_BADARG;
+  }
+  if (!send || !save_mean || !save_invstd || (N > 0 && (!x || !dy))) {
+    set_error("bn_sync_bwd_local: null pointer");
+    return SSDK_E_BADARG;
+  }
+  if (N == 0) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(send, 0, 2 * (size_t)C * sizeof(float), st) != hipSuccess ||
+        (dweight && hipMemsetAsync(dweight, 0, (size_t)C * sizeof(float), st) != hipSuccess) ||
+        (dbias && hipMemsetAsync(dbias, 0, (size_t)C * sizeof(float), st) != hipSuccess))
+      return check_launch("bn_sync_bwd_local");
+    return SSDK_OK;
+  }
+  BnParams p;
+  memset(&p, 0, sizeof(p));
+  rc = bn_common(p, "bn_sync_bwd_local", N, C, HW, dtype, workspace, workspace_bytes);
+  if (rc) return rc;
+  p.x = x;
+  p.dy = dy;
+  p.weight = weight;
+  p.bias = bias;
+  p.act = act;
+  p.save_mean = const_cast<float*>(save_mean);
+  p.save_invstd = const_cast<float*>(save_invstd);
+  p.dweight = dweight;
+  p.dbias = dbias;
+  p.send = send;
+  p.no_apply = 1;
+  bn_launch<1>(p, (hipStream_t)stream);
+  return check_launch("bn_sync_bwd_local");
+}
+
+extern "C" int ssdk_bn_sync_bwd_apply(const void* x, const void* dy, const float* gathered, int W, const float* fwd_gathered,
+                                      const float* weight, const float* bias, const float* save_mean, const float* save_invstd,
+                                      void* dx, int N, int C, int HW, int act, int dtype, void* stream) {
+  int rc = bn_sync_check("bn_sync_bwd_apply", N, C, HW, dtype);
+  if (rc) return rc;
+  if (W < 1 || act < 0 || act > 2) {
+    set_error("bn_sync_bwd_apply: bad arguments W=%d act=%d", W, act);
+    return SSDK_E_BADARG;
+  }
+  if (!gathered || !fwd_gathered || !save_mean || !save_invstd || (N > 0 && (!x || !dy || !dx))) {
+    set_error("bn_sync_bwd_apply: null pointer");
+    return SSDK_E_BADARG;
+  }
+  if (N == 0) return SSDK_OK;
+  BnParams p;
+  memset(&p, 0, sizeof(p));
+  rc = bn_shape(p, "bn_sync_bwd_apply", N, C, HW, dtype);
+  if (rc) return rc;
+  p.x = x;
+  p.dy = dy;
+  p.out = dx;
+  p.weight = weight;
+  p.bias = bias;
+  p.act = act;
+  p.save_mean = const_cast<float*>(save_mean);
+  p.save_invstd = const_cast<float*>(save_invstd);
+  p.gathered = gathered;
+  p.fwd_gathered = fwd_gathered;
+  p.W = W;
+  p.apply_only = 1;
+  bn_launch<1>(p, (hipStream_t)stream);
+  return check_launch("bn_sync_bwd_apply");
 }

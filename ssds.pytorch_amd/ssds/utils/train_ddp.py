@@ -5,8 +5,10 @@ main :193-220) on torch DDP over RCCL/xGMI instead of Apex DDP/AMP/SyncBN over N
         -m ssds.utils.train_ddp -cfg experiments/cfgs/ssd_mobilenetv2_512.yml --steps 100
 
 One process per GPU; ``nccl`` backend == RCCL on ROCm.  bf16 autocast replaces AMP O1 / static loss scale
-128 (bf16 has fp32's exponent range: no loss scaling).  BatchNorm stays local (per-GPU batch 64; set
-``--sync-bn`` for torch SyncBatchNorm).  Gradients: bucketed all-reduce (mean) overlapped with backward;
+128 (bf16 has fp32's exponent range: no loss scaling).  BatchNorm stays local (per-GPU batch 64); ``--sync-bn``
+computes its batch statistics over all ranks (the reference's convert_syncbn_model) on the same BatchNorm kernels and
+fusions, split at one all-gather per direction (batchnorm.use_fast_sync_batchnorm; ``SSDK_FAST_BN=0 --sync-bn``: torch's
+SyncBatchNorm).  Gradients: bucketed all-reduce (mean) overlapped with backward;
 16 MB buckets keep every xGMI ring message bandwidth-bound for the 44 MB of SSD-MobileNetV2 gradients.
 Data: synthetic COCO-shaped batches (ssds/dataset/synthetic.py); the reference's DALI loaders are out of
 scope."""
@@ -34,12 +36,16 @@ class Solver(object):
             print("===> Building model")
         self.model = model_builder.create_model(cfg.MODEL)
         self.load_model()
-        if sync_bn:
+        fast_bn = os.environ.get("SSDK_FAST_BN", "1") != "0"
+        if sync_bn and not fast_bn:
             self.model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(self.model)
-        elif os.environ.get("SSDK_FAST_BN", "1") != "0":
-            from ssds.modeling.layers.batchnorm import use_fast_batchnorm
+        elif fast_bn:
+            from ssds.modeling.layers.batchnorm import use_fast_batchnorm, use_fast_sync_batchnorm
 
-            use_fast_batchnorm(self.model)  # training BN on the ssdk kernels (local statistics, like the default)
+            if sync_bn:
+                use_fast_sync_batchnorm(self.model)  # statistics over all ranks, on the same kernels and fusions
+            else:
+                use_fast_batchnorm(self.model)  # training BN on the ssdk kernels (local statistics, like the default)
             if os.environ.get("SSDK_FUSE_BN_ACT", "1") != "0":
                 from ssds.modeling.layers.batchnorm import fuse_bn_activations
 
@@ -51,10 +57,10 @@ class Solver(object):
             from ssds.modeling.layers.pointwise import use_pointwise_gemm
 
             use_pointwise_gemm(self.model)  # 1x1 convolutions on the NCHW tensors (16 bit: csrc/ssdk_pwtrain.hip; fp32: library GEMMs)
-            if os.environ.get("SSDK_FAST_BN", "1") != "0" and not sync_bn:
+            if fast_bn:
                 from ssds.modeling.layers.pointwise import fuse_conv_bn_statistics
 
-                fuse_conv_bn_statistics(self.model)  # the 1x1 kernels hand their BatchNorm the batch statistics
+                fuse_conv_bn_statistics(self.model)  # the 1x1 kernels hand their BatchNorm the (local) batch statistics
         from ssds.modeling.layers.pointwise import use_native_stem
 
         use_native_stem(self.model)  # the image-side 3x3 / stride-2 convolution: forward + weight gradient on csrc/ssdk_stemtrain.hip (A/B tools/run/r06_s42.sh: 17.0 vs 17.5 ms per step)

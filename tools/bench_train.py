@@ -2,6 +2,7 @@
     python tools/bench_train.py --steps 10            (1 GPU)
     python tools/bench_train.py --gpus N              (re-executes itself under torch.distributed.run with N ranks)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py --gpus N
+    python tools/bench_train.py --sync-bn 1           (synchronised BatchNorm; at one rank the split path is forced)
 Prints one JSON line on rank 0 (images/sec of the full step: fwd, target assignment, loss, bwd, all-reduce,
 optimizer)."""
 import argparse
@@ -28,6 +29,9 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--channels-last", type=int, default=0)
 ap.add_argument("--gpus", type=int, default=1)
 ap.add_argument("--graph", type=int, default=0, help="1: the whole step as one captured hipGraph (single GPU)")
+ap.add_argument("--sync-bn", type=int, default=0, choices=(0, 1),
+                help="1: synchronised BatchNorm (train_ddp --sync-bn); at one rank the split path is forced, so its extra launches "
+                     "are measured")
 ap.add_argument("--size", type=int, default=0, help="square input size instead of the config's (300: planes that are not a multiple of 8)")
 ap.add_argument("--cpu", type=int, default=0,
                 help="(tests/test_ddp_cpu.py) 1: ONLY the launcher / rank / barrier / MAX-time / rank-0-print logic of this "
@@ -76,7 +80,13 @@ if args.cpu:
     mwl = images = targets = anchors = None
     solver = argparse.Namespace(optimizer=None)
 else:
-    solver = Solver(cfg, lr, dev)
+    solver = Solver(cfg, lr, dev, sync_bn=bool(args.sync_bn))
+    if args.sync_bn and world == 1:
+        from ssds.modeling.layers.batchnorm import FastBatchNorm2d
+
+        for m in solver.model.modules():
+            if type(m) is FastBatchNorm2d and m._ssdk_sync:
+                m._ssdk_force_sync = True
     if args.channels_last:
         solver.model.to(memory_format=torch.channels_last)
     mwl = solver.wrap()
@@ -120,7 +130,7 @@ if world > 1:
 if rank == 0:
     print(json.dumps({"metric": "images/sec (DDP training step) SSD-MobileNetV2@%d" % cfg.MODEL.IMAGE_SIZE[0], "value": round(world * args.batch * args.steps / el, 1),
                       "n_gpus": world, "ms_per_step": round(el / args.steps * 1e3, 2), "batch_per_gpu": args.batch,
-                      "cls_loss": float(c), "loc_loss": float(l), "dtype": "bf16 autocast", "hipgraph": bool(args.graph),
+                      "cls_loss": float(c), "loc_loss": float(l), "dtype": "bf16 autocast", "hipgraph": bool(args.graph), "sync_bn": bool(args.sync_bn),
                       "data": "synthetic" if not args.cpu else "stub (CPU / gloo run of the rank logic)"}))
 if world > 1:
     dist.destroy_process_group()
