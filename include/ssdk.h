@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 244 /* 0.2.4.4: ssdk_im2col3x3_folded / ssdk_col2im3x3_folded; 0.2.4.3: ssdk_stem3x3s2_fwd / _wgrad (the first convolution of the training step); 0.2.4.2: ssdk_concat_nchw_to_nhwc; 0.2.4.1: ssdk_pack_conv3x3[_dgrad]; 0.2.4: ssdk_abi_check, ssdk_pw_* (1x1 convolutions of the training step: forward / input gradient / weight gradient on NCHW tensors); 0.2.3: ssdk_struct_size; 0.2.2: ssdk_mbconv_desc.image_nw / w_image / w_image_bytes (ssdk_mbk.hip), larger ssdk_match_multibox_loss workspace; 0.2.1: ssdk_match_multibox_loss, ssdk_op.lane == 2; fields appended to descriptors since 200 (zero = old behaviour) */
+#define SSDK_VERSION 245 /* 0.2.4.5: the BatchNorm workspace begins with ticket words that must be zero when it is first used (ssdk_bn_workspace_bytes); 0.2.4.4: ssdk_im2col3x3_folded / ssdk_col2im3x3_folded; 0.2.4.3: ssdk_stem3x3s2_fwd / _wgrad (the first convolution of the training step); 0.2.4.2: ssdk_concat_nchw_to_nhwc; 0.2.4.1: ssdk_pack_conv3x3[_dgrad]; 0.2.4: ssdk_abi_check, ssdk_pw_* (1x1 convolutions of the training step: forward / input gradient / weight gradient on NCHW tensors); 0.2.3: ssdk_struct_size; 0.2.2: ssdk_mbconv_desc.image_nw / w_image / w_image_bytes (ssdk_mbk.hip), larger ssdk_match_multibox_loss workspace; 0.2.1: ssdk_match_multibox_loss, ssdk_op.lane == 2; fields appended to descriptors since 200 (zero = old behaviour) */
 
 #define SSDK_MAX_LEVELS 8    /* feature-map levels per decode_nms call            */
 #define SSDK_MAX_ANCHORS 16  /* anchors per location (A)                          */
@@ -527,7 +527,12 @@ int ssdk_dwconv_plan(int pass, int N, int C, int H, int W, int stride, int dtype
  *   fwd: y = (x - mean_c) * invstd_c * weight_c + bias_c;  save_mean / save_invstd fp32 [C] (for backward);
  *        running_mean / running_var (may both be NULL) updated like torch: momentum, unbiased variance
  *   bwd: dx, dweight = sum(dy * xhat), dbias = sum(dy)   (dweight / dbias may be NULL)
- * Reductions run in a fixed order (bit-reproducible).  workspace: ssdk_bn_workspace_bytes(N, C), 16-byte aligned. */
+ * Reductions run in a fixed order (bit-reproducible).  workspace: ssdk_bn_workspace_bytes(N, C), 16-byte aligned, laid out
+ * [tickets: C uint32 | partial sums | coefficients].  The contract of ssdk_conv's split-K workspace (version 245): the ticket
+ * words are zero when the workspace is first used, and every launch leaves them zero (the reduction's last workgroup of a
+ * channel finishes it and re-arms its ticket).  So one zero-filled workspace serves every call with the same C on one stream;
+ * calls that may run concurrently need workspaces of their own, and so do calls with different C (the partial sums of one C
+ * lie where the ticket words of a larger one are). */
 size_t ssdk_bn_workspace_bytes(int N, int C);
 int ssdk_bn_train_fwd(const void* x, const float* weight, const float* bias, float* running_mean, float* running_var,
                       void* y, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes, int N, int C,
@@ -568,7 +573,8 @@ int ssdk_bn_act_train_bwd(const void* x, const void* dy, const float* weight, co
  * anything back to the host.  A rank with an empty local batch passes N = 0 (its record has count 0 and is skipped).
  *   ssdk_bn_sync_local_stats   send [3C+1] = [s1[C] | s2[C] | pivot[C] | count]: sums of (x - pivot), (x - pivot)^2 with
  *                              pivot = the channel's first element (0 with producer `sums` [C][2], which are only packed),
- *                              count = N * HW as a uint32 bit pattern.  workspace: ssdk_bn_workspace_bytes(N, C).
+ *                              count = N * HW as a uint32 bit pattern.  workspace: ssdk_bn_workspace_bytes(N, C), with
+ *                              zero ticket words, left zero (the contract of the training calls above).
  *   ssdk_bn_sync_fwd_finalize  gathered [W][3C+1] -> save_mean / save_invstd, running statistics (torch semantics with the
  *                              global count), coef [C][4] (16-byte aligned) = (a, b, 0, .) of y = act(a x + b).  Each rank's
  *                              sums are shifted to the first non-empty rank's pivot P: s2 += 2 d s1 + n d^2, s1 += n d, d =
@@ -576,6 +582,7 @@ int ssdk_bn_act_train_bwd(const void* x, const void* dy, const float* weight, co
  *   ssdk_bn_act_apply          y = act(a x + b) from coef (as ssdk_bn_act_train_stats / ssdk_bn_sync_fwd_finalize write it).
  *   ssdk_bn_sync_bwd_local     send [2C] = [sum g | sum g xhat] of the local batch (g = dy masked by the activation);
  *                              dweight / dbias (may be NULL) = these LOCAL sums (torch.nn.SyncBatchNorm's semantics).
+ *                              workspace: as for ssdk_bn_sync_local_stats.
  *   ssdk_bn_sync_bwd_apply     gathered [W][2C] + the forward's gathered [W][3C+1] (global count) -> dx, one launch.
  * Launches per layer: forward 3 (2 when a depthwise convolution applies coef), backward 2, each excluding the collective. */
 int ssdk_bn_sync_local_stats(const void* x, const float* sums, float* send, void* workspace, size_t workspace_bytes, int N, int C,

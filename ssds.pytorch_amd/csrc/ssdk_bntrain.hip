@@ -16,8 +16,6 @@
 // hardtanh_backward launches and one read + one write of every activation tensor in each direction.
 // A workgroup of a reduction pass owns (channel c, slice s): the planes n = s, s + SPLIT, ... of that channel, read
 // with 16-byte vectors; partials are combined by one thread per channel in index order (bit-reproducible).
-#include <atomic>
-
 #include "ssdk_conv_common.h"
 
 namespace ssdk {
@@ -42,8 +40,8 @@ struct BnParams {
   int N, C, HW, split, dtype;
   float momentum, eps;
   int act;                 // 0 none | 1 ReLU6 | 2 ReLU fused behind the normalisation
-  u32* tickets;            // [C] arrival counters of the reduction's workgroups (zero between launches): the LAST workgroup of a
-                           // channel does the finalize arithmetic itself and there is no finalize launch; nullptr: the launch
+  u32* tickets;            // [C] arrival counters of the reduction's workgroups, at the head of the caller's workspace (zero
+                           // between launches): the LAST workgroup of a channel does the finalize arithmetic (bn_fold_finalize)
   // the split (synchronised) BatchNorm -- see the section "synchronised BatchNorm" below
   float* send;             // != nullptr: the finish writes this rank's record (fwd [3C+1], bwd [2C]) instead of finishing
   const float* gathered;   // bwd apply: [W][2C] backward records of all ranks (the apply pass forms its coefficients itself)
@@ -97,7 +95,7 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float (*red)[2]) 
   b = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
 }
 
-template <int DT, int MODE> __device__ __forceinline__ void bn_fold_finalize(const BnParams& p, int c, int s, float a, float b);  // (below the finalize kernels)
+template <int DT, int MODE> __device__ __forceinline__ void bn_fold_finalize(const BnParams& p, int c, int s, float a, float b);  // (below)
 
 // MODE 0: sums of (x - pivot), (x - pivot)^2.  MODE 1: sums of dy, dy * (x - mean) * invstd.
 template <int DT, int MODE>
@@ -151,12 +149,7 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const BnParams p) {
     }
   }
   block_sum2(a, b, red);
-  if (p.tickets) {  // (workgroup-uniform)
-    bn_fold_finalize<DT, MODE>(p, c, s, a, b);
-  } else if (threadIdx.x == 0) {
-    p.partial[((size_t)c * p.split + s) * 2 + 0] = a;
-    p.partial[((size_t)c * p.split + s) * 2 + 1] = b;
-  }
+  bn_fold_finalize<DT, MODE>(p, c, s, a, b);
 }
 
 // forward statistics -> mean, invstd, running stats, apply coefficients (a, b) of channel c from its sums (s1, s2) of
@@ -192,21 +185,12 @@ __device__ __forceinline__ void bn_fwd_finish(const BnParams& p, int c, float s1
   }
   bn_fwd_out(p, c, (float)p.N * (float)p.HW, pivot, s1, s2);
 }
+// the forward statistics from raw sums handed over by the producing convolution (pivot 0): there is no reduction to fold into
 template <int DT>
 __global__ __launch_bounds__(64) void bn_fwd_finalize_kernel(const BnParams p) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= p.C) return;
-  float s1 = 0.f, s2 = 0.f;
-  if (p.sums) {  // raw sums from the producing convolution: pivot 0
-    s1 = p.sums[2 * c + 0];
-    s2 = p.sums[2 * c + 1];
-  } else {
-    for (int s = 0; s < p.split; ++s) {
-      s1 += p.partial[((size_t)c * p.split + s) * 2 + 0];
-      s2 += p.partial[((size_t)c * p.split + s) * 2 + 1];
-    }
-  }
-  bn_fwd_finish<DT>(p, c, s1, s2);
+  bn_fwd_finish<DT>(p, c, p.sums[2 * c + 0], p.sums[2 * c + 1]);
 }
 
 // backward sums (over M elements) -> coefficients (a, k0, k1, forward offset) of dx = a*dy + k1*x + k0
@@ -232,16 +216,6 @@ __device__ __forceinline__ void bn_bwd_finish(const BnParams& p, int c, float sg
   p.coef[c * 4 + 1] = k.y;
   p.coef[c * 4 + 2] = k.z;
   p.coef[c * 4 + 3] = k.w;
-}
-__global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const BnParams p) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  if (c >= p.C) return;
-  float sg = 0.f, sgx = 0.f;
-  for (int s = 0; s < p.split; ++s) {
-    sg += p.partial[((size_t)c * p.split + s) * 2 + 0];
-    sgx += p.partial[((size_t)c * p.split + s) * 2 + 1];
-  }
-  bn_bwd_finish(p, c, sg, sgx);
 }
 
 // ---- synchronised BatchNorm: statistics over the batches of all ranks of a process group ----------------------------------
@@ -301,8 +275,8 @@ __device__ __forceinline__ float4 bn_sync_bwd_coef(const BnParams& p, int c) {
 
 // The finalize arithmetic WITHOUT its launch (round 6: 90 finalize launches of ~5 us per training step).  Every workgroup of
 // a reduction publishes its partial sums (a, b) and draws a ticket of its channel; the one that draws the last ticket reads
-// the channel's partials back, adds them in INDEX order -- the order of the finalize kernels, so the statistics keep their
-// bits -- and does what the finalize kernel's thread of that channel does.  It leaves the ticket at zero for the next launch.
+// the channel's partials back, adds them in INDEX order (the order of the finalize launch this replaced, so the statistics
+// keep their bits) and finishes the channel.  It leaves the ticket at zero for the next launch on the same workspace.
 // The partials travel between CUs of different XCDs (one L2 each) as agent-scope relaxed atomics: the store goes through to
 // memory, the load does not take a line from the reader's L2.  (NOT fences: an agent-scope release is a write-back of the
 // whole L2, full of the neighbouring passes' dirty lines -- measured, 17.6 -> 22-29 ms per step.)  split <= 64 (bn_split).
@@ -501,12 +475,7 @@ __global__ __launch_bounds__(256) void bn_reduce_flat_kernel(const BnParams p) {
     }
   }
   block_sum2(a, b, red);
-  if (p.tickets) {  // (workgroup-uniform)
-    bn_fold_finalize<DT, MODE>(p, c, s, a, b);
-  } else if (threadIdx.x == 0) {
-    p.partial[((size_t)c * p.split + s) * 2 + 0] = a;
-    p.partial[((size_t)c * p.split + s) * 2 + 1] = b;
-  }
+  bn_fold_finalize<DT, MODE>(p, c, s, a, b);
 }
 
 struct BnFlat {
@@ -610,31 +579,12 @@ static int bn_split(int N, int C) {
   return s < 1 ? 1 : s;
 }
 
-// Ticket words of the folded finalize: kBnTicketRegions regions of kBnTicketC channels in device memory, zero when the module
-// is loaded and left at zero by every launch that uses them.  Consecutive launches take consecutive regions, so BatchNorms
-// that run concurrently on two streams do not share counters unless more than kBnTicketRegions of them are in flight.
-constexpr int kBnTicketC = 2048, kBnTicketRegions = 16;
-__device__ u32 g_bn_tickets[kBnTicketRegions * kBnTicketC];
-
-static u32* bn_tickets(int C) {
-  if (C > kBnTicketC) return nullptr;  // (A/B on the 512 px training step, tools/run/r06_s34.sh: 17.43 / 17.44 ms folded, 17.56 / 17.62 ms with the launch)
-  static u32* base[16] = {};  // per device (the symbol has one address per device)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!base[dev]) {
-    void* a = nullptr;
-    if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_bn_tickets)) != hipSuccess || !a) return nullptr;
-    base[dev] = (u32*)a;
-  }
-  static std::atomic<unsigned> turn{0};
-  return base[dev] + (size_t)(turn.fetch_add(1u) % (unsigned)kBnTicketRegions) * kBnTicketC;
-}
+// Workspace: ticket words [C] u32 | partial sums [C][split][2] | coefficient table [C][4], each part 16-byte aligned.  The
+// ticket words come first and their place depends on C alone, so launches with the same C never see them hold anything else.
+static size_t bn_round4(size_t n) { return (n + 3) & ~(size_t)3; }
 
 template <int MODE>
-static void bn_launch(const BnParams& p0, hipStream_t st) {
-  BnParams p = p0;
-  const bool has_reduce = !(MODE == 0 && p.sums) && !p.apply_only;
-  p.tickets = has_reduce ? bn_tickets(p.C) : nullptr;  // the reduction finalizes (no finalize launch)
+static void bn_launch(const BnParams& p, hipStream_t st) {
   // 0: the per-plane kernels, 1: the flat kernels, 2 (default): the flat reduction always, the flat apply pass only where
   // the per-plane one cannot use vectors (plane size not a multiple of the vector width, or a misaligned tensor: there it
   // works element by element).  Per launch on the 512 px step, bf16 (profiles/r02_train_kernel_split_v2.txt against a trace
@@ -657,12 +607,10 @@ static void bn_launch(const BnParams& p0, hipStream_t st) {
   const dim3 agrid((unsigned)((p.HW + 256 * vn - 1) / (256 * vn)), (unsigned)NC);
 #define SSDK_BN(DT)                                                                                         \
   do {                                                                                                      \
-    if ((MODE == 0 && p.sums) || p.apply_only) {                                                            \
+    if (MODE == 0 && p.sums) hipLaunchKernelGGL((bn_fwd_finalize_kernel<DT>), dim3((unsigned)((p.C + 63) / 64)), dim3(64), 0, st, p); \
+    else if (p.apply_only) {                                                                                 \
     } else if (flat_r) hipLaunchKernelGGL((bn_reduce_flat_kernel<DT, MODE>), rgrid, dim3(256), 0, st, p);   \
     else hipLaunchKernelGGL((bn_reduce_kernel<DT, MODE>), rgrid, dim3(256), 0, st, p);                      \
-    if (p.tickets || p.apply_only) {                                                                        \
-    } else if (MODE == 0) hipLaunchKernelGGL((bn_fwd_finalize_kernel<DT>), dim3((unsigned)((p.C + 63) / 64)), dim3(64), 0, st, p); \
-    else hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((p.C + 63) / 64)), dim3(64), 0, st, p);  \
     if (p.no_apply) {                                                                                        \
     } else if (MODE == 1 && p.gathered) {                                                                    \
       if (flat && fgrid < (1l << 31)) hipLaunchKernelGGL((bn_apply_flat_kernel<DT, MODE, MODE == 1>), dim3((unsigned)fgrid), dim3(256), 0, st, p, f); \
@@ -681,8 +629,7 @@ static void bn_launch(const BnParams& p0, hipStream_t st) {
 using namespace ssdk;
 
 extern "C" size_t ssdk_bn_workspace_bytes(int N, int C) {
-  // partial sums [C][split][2], rounded up to a multiple of 4 floats (the coefficient table behind it stays 16-byte aligned)
-  return ((((size_t)C * bn_split(N, C) * 2 + 3) & ~(size_t)3) + (size_t)C * 4) * sizeof(float);
+  return (bn_round4((size_t)C) + bn_round4((size_t)C * bn_split(N, C) * 2) + (size_t)C * 4) * sizeof(float);
 }
 
 static int bn_shape(BnParams& p, const char* what, int N, int C, int HW, int dtype) {
@@ -705,8 +652,9 @@ static int bn_common(BnParams& p, const char* what, int N, int C, int HW, int dt
     set_error("%s: workspace too small or misaligned", what);
     return SSDK_E_BADARG;
   }
-  p.partial = (float*)workspace;
-  p.coef = p.partial + (((size_t)C * p.split * 2 + 3) & ~(size_t)3);
+  p.tickets = (u32*)workspace;
+  p.partial = (float*)workspace + bn_round4((size_t)C);
+  p.coef = p.partial + bn_round4((size_t)C * p.split * 2);
   return SSDK_OK;
 }
 

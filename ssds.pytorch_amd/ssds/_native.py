@@ -96,7 +96,7 @@ FUSE_SAME, FUSE_UP2, FUSE_POOL2 = 0, 1, 2
 NCHW, NHWC = 0, 1
 
 
-ABI_VERSION = 244  # include/ssdk.h SSDK_VERSION this module's ctypes mirrors and prototypes are written for
+ABI_VERSION = 245  # include/ssdk.h SSDK_VERSION this module's ctypes mirrors and prototypes are written for
 
 
 def _load():
@@ -437,6 +437,22 @@ def workspace(device, nbytes):
         if buf is None or buf.numel() < nbytes:
             buf = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, device=device)
             _ws[key] = buf
+    return buf
+
+
+_scratch = {}
+
+
+def scratch(device, user, nbytes):
+    """Zero-filled, grow-only per-(device, stream) scratch holding arrival counters (split-K slabs, BatchNorm tickets).  The
+    kernels leave their counters at zero, so calls in stream order may share it, and calls on other streams get their own.
+    ``user`` keys one counter layout: users whose layouts differ never share a buffer."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, user)
+    with _ws_lock:
+        buf = _scratch.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.zeros(int(nbytes), dtype=torch.uint8, device=device)
+            _scratch[key] = buf
     return buf
 
 

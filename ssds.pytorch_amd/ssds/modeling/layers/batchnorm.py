@@ -23,8 +23,11 @@ from ssds import _native as N
 
 
 def _ws(dev, n, c):
+    """-> (pointer, bytes) of the BatchNorm workspace for C channels on the current stream: zero-filled once, its ticket words
+    left at zero by every call (include/ssdk.h); one buffer per C, since the ticket words of one C overlap the partial sums of
+    another.  Nothing reads it after the call: records, coefficients and statistics are tensors of their own."""
     need = int(N.lib.ssdk_bn_workspace_bytes(n, c))
-    return torch.empty(need + 16, dtype=torch.uint8, device=dev), need
+    return N.scratch(dev, ("bn", c), need).data_ptr(), need
 
 
 class _BatchNormTrain(torch.autograd.Function):
@@ -39,8 +42,7 @@ class _BatchNormTrain(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(c, device=dev, dtype=torch.float32)
         invstd = torch.empty(c, device=dev, dtype=torch.float32)
-        ws, need = _ws(dev, n, c)
-        wp = (ws.data_ptr() + 15) & ~15
+        wp, need = _ws(dev, n, c)
         with torch.cuda.device(dev):
             if sums is not None:
                 N.check(N.lib.ssdk_bn_act_train_fwd_sums(x.data_ptr(), sums.data_ptr(), weight.data_ptr(), bias.data_ptr(),
@@ -70,8 +72,7 @@ class _BatchNormTrain(torch.autograd.Function):
         gx = torch.empty_like(x)
         gw = torch.empty(c, device=dev, dtype=torch.float32)
         gb = torch.empty(c, device=dev, dtype=torch.float32)
-        ws, need = _ws(dev, n, c)
-        wp = (ws.data_ptr() + 15) & ~15
+        wp, need = _ws(dev, n, c)
         with torch.cuda.device(dev):
             N.check(N.lib.ssdk_bn_act_train_bwd(x.data_ptr(), gy.data_ptr(), weight.data_ptr(), bias.data_ptr(),
                                                 mean.data_ptr(), invstd.data_ptr(), gx.data_ptr(), gw.data_ptr(),
@@ -94,8 +95,7 @@ class _BatchNormDeferred(torch.autograd.Function):
         mean = torch.empty(c, device=dev, dtype=torch.float32)
         invstd = torch.empty(c, device=dev, dtype=torch.float32)
         coef = torch.empty((c, 4), device=dev, dtype=torch.float32)
-        ws, need = _ws(dev, n, c)
-        wp = (ws.data_ptr() + 15) & ~15
+        wp, need = _ws(dev, n, c)
         with torch.cuda.device(dev):
             N.check(N.lib.ssdk_bn_act_train_stats(x.data_ptr(), None if sums is None else sums.data_ptr(), weight.data_ptr(),
                                                   bias.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(), mean.data_ptr(),
@@ -145,8 +145,7 @@ def _sync_forward_stats(x, weight, bias, running_mean, running_var, momentum, ep
     hw = int(x.shape[2]) * int(x.shape[3])
     dev = x.device
     send = torch.empty(3 * c + 1, device=dev, dtype=torch.float32)
-    ws, need = _ws(dev, max(n, 1), c)
-    wp = (ws.data_ptr() + 15) & ~15
+    wp, need = _ws(dev, max(n, 1), c)
     with torch.cuda.device(dev):
         N.check(N.lib.ssdk_bn_sync_local_stats(_ptr(x), None if sums is None else sums.data_ptr(), send.data_ptr(), wp, need, n, c,
                                                hw, N.dtype_code(x), N.stream_ptr(dev)), "bn_sync_local_stats")
@@ -195,8 +194,7 @@ class _SyncBatchNormTrain(torch.autograd.Function):
         send = torch.empty(2 * c, device=dev, dtype=torch.float32)
         gw = torch.empty(c, device=dev, dtype=torch.float32)
         gb = torch.empty(c, device=dev, dtype=torch.float32)
-        ws, need = _ws(dev, max(n, 1), c)
-        wp = (ws.data_ptr() + 15) & ~15
+        wp, need = _ws(dev, max(n, 1), c)
         with torch.cuda.device(dev):
             N.check(N.lib.ssdk_bn_sync_bwd_local(_ptr(x), _ptr(gy), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(),
                                                  invstd.data_ptr(), send.data_ptr(), gw.data_ptr(), gb.data_ptr(), wp, need, n, c,

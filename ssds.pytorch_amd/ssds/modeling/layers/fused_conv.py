@@ -500,20 +500,6 @@ def fill_desc(d, x_ptr, n, h, w, pack, dtype_code, act, y_ptr, in_layout=N.NHWC,
     return d
 
 
-_SPLITK_WS = {}
-
-
-def _splitk_ws(device, nbytes):
-    """Zero-initialised split-K scratch per (device, stream); the kernels re-arm their counters, so it stays
-    valid across calls as long as calls on it are stream-ordered."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    buf = _SPLITK_WS.get(key)
-    if buf is None or buf.numel() < nbytes + 256:
-        buf = torch.zeros(nbytes + 256, dtype=torch.uint8, device=device)
-        _SPLITK_WS[key] = buf
-    return buf
-
-
 def conv_native(x, pack, act=None, residual=None, nchw_out=False, split=None, act2=None, res_mode=0):
     """One fused layer.  x: [N,C,H,W] tensor in channels_last memory (converted if not; the stem also takes
     plain NCHW).  Returns a channels_last tensor, or NCHW tensor(s) when ``nchw_out`` (heads)."""
@@ -544,7 +530,7 @@ def conv_native(x, pack, act=None, residual=None, nchw_out=False, split=None, ac
     with torch.cuda.device(x.device):
         need = int(N.lib.ssdk_conv_workspace_bytes(n, pack.cin, h, w, pack.cout, pack.k, pack.stride, N.dtype_code(x)))
         if need:
-            ws = _splitk_ws(x.device, need)
+            ws = N.scratch(x.device, "splitk", need + 256)  # (+ 256: the kernels take it 256-byte aligned)
             wptr = (ws.data_ptr() + 255) & ~255
             rc = N.lib.ssdk_conv(ctypes.byref(d), wptr, ws.numel() - (wptr - ws.data_ptr()), N.stream_ptr(x.device))
         else:

@@ -75,7 +75,7 @@ class _HeadPair3x3(torch.autograd.Function):
                              y2.data_ptr(), nl, "none")
             need = int(N.lib.ssdk_conv_workspace_bytes(n, cin, h, w, rows, 3, 1, N.dtype_code(x)))
             if need:
-                ws = FC._splitk_ws(dev, need)
+                ws = N.scratch(dev, "splitk", need + 256)
                 wptr = (ws.data_ptr() + 255) & ~255
                 rc = N.lib.ssdk_conv(ctypes_byref(d), wptr, ws.numel() - (wptr - ws.data_ptr()), sp)
             else:
@@ -200,7 +200,7 @@ def _input_gradient(gl, gc, wl, wc, x):
         d = FC.fill_desc(N.ConvDesc(), g.data_ptr(), n, h, w, pk, N.dtype_code(x), "none", gx.data_ptr(), N.NHWC, N.NCHW)
         need = int(N.lib.ssdk_conv_workspace_bytes(n, opad, h, w, cin, 3, 1, N.dtype_code(x)))
         if need:
-            ws = FC._splitk_ws(dev, need)
+            ws = N.scratch(dev, "splitk", need + 256)
             wptr = (ws.data_ptr() + 255) & ~255
             rc = N.lib.ssdk_conv(ctypes_byref(d), wptr, ws.numel() - (wptr - ws.data_ptr()), sp)
         else:

@@ -223,7 +223,9 @@ class GraphedTrainStep(object):
         torch.cuda.current_stream(dev).wait_stream(side)
         optimizer.zero_grad(set_to_none=True)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        # captured on the warm-up stream: the zero-filled per-stream scratch of the kernels (_native.scratch) already exists
+        # there, so the graph allocates none and holds no fill of it
+        with torch.cuda.graph(self.graph, stream=side):
             with torch.autocast(device_type="cuda", dtype=autocast_dtype, enabled=autocast_dtype is not None):
                 cls_loss, loc_loss, _, _ = model_with_loss(self.images, self.targets, anchors)
                 total = cls_loss + loc_loss

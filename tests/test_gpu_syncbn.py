@@ -78,7 +78,7 @@ def _ws(n, c):
     from ssds import _native as N
 
     need = int(N.lib.ssdk_bn_workspace_bytes(max(n, 1), c))
-    return torch.empty(need, dtype=torch.uint8, device="cuda"), need
+    return torch.zeros(need, dtype=torch.uint8, device="cuda"), need  # (zero ticket words: include/ssdk.h)
 
 
 def _ptr(t):

@@ -425,6 +425,137 @@ def test_batchnorm_with_folded_activation_is_bit_identical_to_the_two_step_path(
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dtype_name", ["float32", "bfloat16"])
+def test_batchnorm_entry_points_leave_the_ticket_words_zero(dtype_name):
+    """The workspace contract (include/ssdk.h, version 245): every entry point that reduces leaves the ticket words [C] at the
+    head of its workspace zero, so the next call on the same workspace counts from zero again."""
+    import torch
+    from ssds import _native as N
+
+    L, st = N.lib, N.stream_ptr(torch.device("cuda"))
+    dtype = getattr(torch, dtype_name)
+    torch.manual_seed(1)
+    for n, c, h, w in ((4, 32, 16, 24), (3, 17, 9, 7), (2, 2304, 5, 5)):
+        hw = h * w
+        x = (torch.randn(n, c, h, w, device="cuda") * 2 + 3).to(dtype)
+        dy = torch.randn_like(x)
+        y, dx = torch.empty_like(x), torch.empty_like(x)
+        weight, bias = torch.rand(c, device="cuda") + 0.5, torch.randn(c, device="cuda")
+        rm, rv = torch.zeros(c, device="cuda"), torch.ones(c, device="cuda")
+        mean, invstd, dw, db = (torch.empty(c, device="cuda") for _ in range(4))
+        coef, send = torch.empty(c, 4, device="cuda"), torch.empty(3 * c + 1, device="cuda")
+        need = int(L.ssdk_bn_workspace_bytes(n, c))
+        ws = torch.zeros(need, dtype=torch.uint8, device="cuda")
+        tickets = ws[:4 * c].view(torch.int32)
+        P = lambda t: t.data_ptr()  # noqa: E731
+        dc, wp = N.dtype_code(x), ws.data_ptr()
+        calls = (
+            ("fwd", lambda: L.ssdk_bn_act_train_fwd(P(x), P(weight), P(bias), P(rm), P(rv), P(y), P(mean), P(invstd), wp, need, n, c,
+                                                    hw, 0.1, 1e-5, 1, dc, st)),
+            ("stats", lambda: L.ssdk_bn_act_train_stats(P(x), None, P(weight), P(bias), P(rm), P(rv), P(mean), P(invstd), P(coef), wp,
+                                                        need, n, c, hw, 0.1, 1e-5, dc, st)),
+            ("bwd", lambda: L.ssdk_bn_act_train_bwd(P(x), P(dy), P(weight), P(bias), P(mean), P(invstd), P(dx), P(dw), P(db), wp, need,
+                                                    n, c, hw, 1, dc, st)),
+            ("sync_local_stats", lambda: L.ssdk_bn_sync_local_stats(P(x), None, P(send), wp, need, n, c, hw, dc, st)),
+            ("sync_bwd_local", lambda: L.ssdk_bn_sync_bwd_local(P(x), P(dy), P(weight), P(bias), P(mean), P(invstd), P(send), P(dw),
+                                                                P(db), wp, need, n, c, hw, 1, dc, st)),
+        )
+        for name, call in calls:
+            N.check(call(), name)
+            torch.cuda.synchronize()
+            assert int(tickets.count_nonzero()) == 0, "%s (C=%d) left ticket words set" % (name, c)
+
+
+@pytest.mark.gpu
+def test_batchnorm_on_two_streams_has_no_cross_talk():
+    """About 40 BatchNorm forward + backward calls of different shapes, alternating between two streams with no synchronisation
+    in between, give the bits of the same calls one after another on one stream: each stream has its own workspaces."""
+    import torch
+    from ssds.modeling.layers.batchnorm import FastBatchNorm2d
+
+    shapes = [(4, 32, 16, 24), (3, 17, 9, 7), (2, 144, 13, 13), (8, 96, 20, 20), (2, 2304, 5, 5), (16, 24, 38, 38), (5, 7, 19, 19)]
+    torch.manual_seed(2)
+    cases = []
+    for i in range(42):
+        n, c, h, w = shapes[i % len(shapes)]
+        dtype = torch.bfloat16 if i % 3 else torch.float32
+        bn = FastBatchNorm2d(c)
+        bn.weight.data.uniform_(0.5, 1.5)
+        bn.bias.data.normal_(0, 0.3)
+        bn._ssdk_act = i % 3  # none / ReLU6 / ReLU folded in
+        cases.append((bn.cuda().train(), (torch.randn(n, c, h, w, device="cuda") * 2 + 3).to(dtype),
+                      torch.randn(n, c, h, w, device="cuda").to(dtype)))
+    state = [{k: v.clone() for k, v in bn.state_dict().items()} for bn, _, _ in cases]
+
+    def run(streams):
+        out = []
+        for i, (bn, x, g) in enumerate(cases):
+            bn.load_state_dict(state[i])
+            bn.weight.grad = bn.bias.grad = None
+            s = streams[i % len(streams)]
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                xi = x.detach().clone().requires_grad_(True)
+                y = bn(xi)
+                y.backward(g)
+                out.append((y.detach(), xi.grad, bn.weight.grad, bn.bias.grad, bn.running_mean.clone(), bn.running_var.clone()))
+        for s in streams:
+            torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        return out
+
+    two = run([torch.cuda.Stream(), torch.cuda.Stream()])
+    one = run([torch.cuda.current_stream()])
+    for i, (a, b) in enumerate(zip(two, one)):
+        for what, u, v in zip(("y", "dx", "dweight", "dbias", "running_mean", "running_var"), a, b):
+            assert torch.equal(u, v), "call %d %s: %s differs between two streams and one" % (i, cases[i][1].shape, what)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("dtype_name,tol", [("float32", 2e-4), ("bfloat16", 2e-2), ("float16", 4e-3)])
+def test_batchnorm_above_2048_channels_matches_torch(dtype_name, tol, split):
+    """C = 2304, above the 2048 channels the tickets once covered (such layers took a separate finalize launch): forward and
+    backward, local and the one-rank split path, against nn.BatchNorm2d with the tolerances of
+    test_batchnorm_training_kernels_match_torch; two runs give the same bits."""
+    import torch
+    import torch.nn as nn
+    from ssds.modeling.layers.batchnorm import FastBatchNorm2d
+
+    n, c, h, w = 4, 2304, 6, 5
+    dtype = getattr(torch, dtype_name)
+    torch.manual_seed(3)
+    ref = nn.BatchNorm2d(c).cuda().train()
+    ref.weight.data.uniform_(0.5, 1.5)
+    ref.bias.data.normal_(0, 0.3)
+    ref.running_mean.normal_(0, 0.2)
+    ref.running_var.uniform_(0.5, 1.5)
+    state = {k: v.clone() for k, v in ref.state_dict().items()}
+    x = (torch.randn(n, c, h, w, device="cuda") * 2 + 3).to(dtype)
+    x32 = x.detach().float().clone().requires_grad_(True)
+    yr = ref(x32)
+    g = torch.randn_like(yr)
+    yr.backward(g)
+
+    def run():
+        fast = FastBatchNorm2d(c).cuda().train()
+        fast.load_state_dict(state)
+        fast._ssdk_sync = fast._ssdk_force_sync = split  # (world size 1: the split entry points around an identity gather)
+        xf = x.detach().clone().requires_grad_(True)
+        yf = fast(xf)
+        assert yf.dtype == dtype
+        yf.backward(g.to(dtype))
+        return [yf.detach(), xf.grad, fast.weight.grad, fast.bias.grad, fast.running_mean, fast.running_var]
+
+    got, again = run(), run()
+    for what, a, b, r in zip(("output", "dx", "dweight", "dbias", "running_mean", "running_var"), got, again,
+                             (yr, x32.grad, ref.weight.grad, ref.bias.grad, ref.running_mean, ref.running_var)):
+        err = float((a.float() - r.float()).abs().max()) / max(float(r.abs().max()), 1e-6)
+        assert err < tol, "%s: rel err %.3g" % (what, err)
+        assert torch.equal(a, b), "%s: two runs differ" % what
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("dtype_name,tol", [("float32", 2e-4), ("bfloat16", 2e-2), ("float16", 4e-3)])
 @pytest.mark.parametrize("n,cin,cout,h,w,bias", [
     (4, 16, 96, 16, 24, False), (3, 24, 144, 9, 7, True), (64, 160, 960, 16, 16, False), (2, 320, 256, 5, 5, True),

@@ -208,4 +208,4 @@ def test_sync_entry_points_are_declared_and_exported():
     for name in ("ssdk_bn_sync_local_stats", "ssdk_bn_sync_fwd_finalize", "ssdk_bn_act_apply", "ssdk_bn_sync_bwd_local",
                  "ssdk_bn_sync_bwd_apply"):
         assert name in N.EXPORTS and name + "(" in hdr and hasattr(N.lib, name)
-    assert N.lib.ssdk_version() == 244
+    assert N.lib.ssdk_version() == 245
