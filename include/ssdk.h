@@ -482,6 +482,26 @@ int ssdk_concat_nchw_to_nhwc(const void* a, int c1, const void* b, int c2, void*
 int ssdk_sgd_step(int n, void* const* params, const void* const* grads, void* const* momentum_bufs, const int64_t* numel,
                   const float* lr_dev, float lr, float momentum, float weight_decay, int nesterov, const float* found_inf,
                   void* stream);
+/* Adam / AMSGrad over ALL parameter tensors of a model (csrc/ssdk_sgd.hip): torch.optim.Adam's update (the reference's
+ * `adam` / `amsgrad`, core/optimizer.py:73-134; no decoupled weight decay, no maximize) in torch's per-element operation order.
+ * fp32 tensors.  params / grads / exp_avg / exp_avg_sq / max_exp_avg_sq / steps / numel are HOST arrays of n entries (device
+ * pointers, element counts); max_exp_avg_sq may be NULL unless amsgrad; steps[i] = the tensor's step counter (torch's
+ * state["step"]: an fp32 device scalar).
+ *   s = step + 1;  g = grad + weight_decay p;  m = lerp(m, g, 1 - beta1);  v = beta2 v + (1 - beta2) g g;
+ *   amsgrad: vmax = max(vmax, v);  p -= (lr / (1 - beta1^s)) m / (sqrt(v | vmax) / sqrt(1 - beta2^s) + eps)   (powers in fp64)
+ * One small launch after the update launches advances every counter by 1.  lr_dev (device float, may be NULL -> lr) is read by
+ * the kernel: a captured hipGraph sees later changes.  found_inf (device float, may be NULL): non-zero = no tensor and no
+ * counter is touched.  SSDK_E_BADARG (nothing launched): n < 0, a NULL array or pointer, a tensor of >= 2^32 elements. */
+int ssdk_adam_step(int n, void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq,
+                   void* const* max_exp_avg_sq, void* const* steps, const int64_t* numel, const float* lr_dev, float lr,
+                   double beta1, double beta2, float eps, float weight_decay, int amsgrad, const float* found_inf, void* stream);
+/* RMSprop (torch's non-centered rule, the reference's `rmsprop`), same conventions as ssdk_adam_step; momentum_bufs may be NULL
+ * when momentum == 0.  The counters are advanced (torch keeps them) but the rule does not read them.
+ *   g = grad + weight_decay p;  sq = alpha sq + (1 - alpha) g g;  avg = sqrt(sq) + eps;
+ *   momentum: buf = momentum buf + g / avg;  p -= lr buf        otherwise: p -= lr g / avg */
+int ssdk_rmsprop_step(int n, void* const* params, const void* const* grads, void* const* square_avg, void* const* momentum_bufs,
+                      void* const* steps, const int64_t* numel, const float* lr_dev, float lr, double alpha, float eps,
+                      float weight_decay, float momentum, const float* found_inf, void* stream);
 
 /* Depthwise 3x3 convolution (pad 1, stride 1|2) for the TRAINING step: forward, input gradient and weight gradient,
  * NCHW contiguous, dtype SSDK_F32 | SSDK_BF16 | SSDK_F16, fp32 accumulation (replaces MIOpen's naive_conv_* kernels

@@ -119,11 +119,14 @@ def _ensure_momentum_buffers(optimizer, every=False):
     """Zero momentum buffers for every parameter that has none yet.  torch's fused SGD allocates them with ``empty_like``
     inside its first step and returns early when ``found_inf`` is set: a skipped FIRST step would leave uninitialised
     memory behind as momentum.  With zero buffers in place the first real step computes ``0 * momentum + grad`` -- exactly
-    the first-step rule (dampening is 0 in core/optimizer.configure_optimizer)."""
-    from ssds.core.optimizer import SsdkSGD
+    the first-step rule (dampening is 0 in core/optimizer.configure_optimizer).  The optimizers on csrc/ssdk_sgd.hip create
+    their whole state (Adam's moments and step counters too) through ``init_state``."""
+    from ssds.core.optimizer import SsdkOptimizer
 
-    if isinstance(optimizer, SsdkSGD) and not every:
-        return  # (csrc/ssdk_sgd.hip's host side creates missing buffers as zeros itself, skipped step or not)
+    if isinstance(optimizer, SsdkOptimizer):
+        if every:
+            optimizer.init_state(every=True)
+        return  # (per step their host side creates missing state as zeros itself, skipped step or not)
     for group in optimizer.param_groups:
         if not group.get("momentum"):
             continue
@@ -180,13 +183,13 @@ class GraphedTrainStep(object):
         caller's ``param_group["lr"]`` stays a device tensor afterwards -- printing it synchronises, and
         ``optimizer.state_dict()`` would serialise tensors; ``float_lr_state_dict(optimizer)`` returns the state dict with
         plain floats for checkpoints;
-      * momentum, weight decay, nesterov are kernel ARGUMENTS of the captured launch: changing them afterwards needs a new
-        GraphedTrainStep;
+      * momentum, weight decay, nesterov (Adam's betas and eps, RMSprop's alpha) are kernel ARGUMENTS of the captured launch:
+        changing them afterwards needs a new GraphedTrainStep;
       * the ``warmup`` eager steps (>= 1: allocator pools, MIOpen / rocBLAS plans, the optimizer's lazily created state --
         a capture of the very first step would bake ``is_first_step`` in and overwrite the momentum on every replay) run on
         the sample batch but leave NO trace: parameters, buffers (BatchNorm statistics) and the optimizer state are
-        snapshotted before and restored after them (momentum buffers that did not exist are zeroed: see
-        ``_ensure_momentum_buffers``)."""
+        snapshotted before and restored after them (momentum buffers -- the whole state of SsdkAdam / SsdkRMSprop, step
+        counters included -- that did not exist are created as zeros first: see ``_ensure_momentum_buffers``)."""
 
     def __init__(self, model_with_loss, images, targets, anchors, optimizer, autocast_dtype=torch.bfloat16, warmup=3):
         if not (images.is_cuda and _device_skip(optimizer)):

@@ -3,6 +3,7 @@
     python tools/bench_train.py --gpus N              (re-executes itself under torch.distributed.run with N ranks)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py --gpus N
     python tools/bench_train.py --sync-bn 1           (synchronised BatchNorm; at one rank the split path is forced)
+    python tools/bench_train.py --optimizer adam      (cfg.TRAIN.OPTIMIZER.OPTIMIZER: sgd | adam | amsgrad | rmsprop)
 Prints one JSON line on rank 0 (images/sec of the full step: fwd, target assignment, loss, bwd, all-reduce,
 optimizer)."""
 import argparse
@@ -32,6 +33,8 @@ ap.add_argument("--graph", type=int, default=0, help="1: the whole step as one c
 ap.add_argument("--sync-bn", type=int, default=0, choices=(0, 1),
                 help="1: synchronised BatchNorm (train_ddp --sync-bn); at one rank the split path is forced, so its extra launches "
                      "are measured")
+ap.add_argument("--optimizer", default="sgd", choices=("sgd", "adam", "amsgrad", "rmsprop"),
+                help="the config's optimizer (core/optimizer.configure_optimizer: the ssdk kernels on a HIP device)")
 ap.add_argument("--size", type=int, default=0, help="square input size instead of the config's (300: planes that are not a multiple of 8)")
 ap.add_argument("--cpu", type=int, default=0,
                 help="(tests/test_ddp_cpu.py) 1: ONLY the launcher / rank / barrier / MAX-time / rank-0-print logic of this "
@@ -64,6 +67,7 @@ else:
         dist.init_process_group("nccl", device_id=dev)  # "nccl" is RCCL on ROCm
 cfg = config.cfg_from_file(os.path.join(ROOT, "experiments", "cfgs", "ssd_mobilenetv2_512.yml"))
 cfg.TRAIN.BATCH_SIZE = args.batch
+cfg.TRAIN.OPTIMIZER.OPTIMIZER = args.optimizer
 if args.size:
     cfg.MODEL.IMAGE_SIZE = [args.size, args.size]
 cfg.EXP_DIR = "/tmp/ssdk_bench_train"
@@ -131,6 +135,7 @@ if rank == 0:
     print(json.dumps({"metric": "images/sec (DDP training step) SSD-MobileNetV2@%d" % cfg.MODEL.IMAGE_SIZE[0], "value": round(world * args.batch * args.steps / el, 1),
                       "n_gpus": world, "ms_per_step": round(el / args.steps * 1e3, 2), "batch_per_gpu": args.batch,
                       "cls_loss": float(c), "loc_loss": float(l), "dtype": "bf16 autocast", "hipgraph": bool(args.graph), "sync_bn": bool(args.sync_bn),
+                      "optimizer": args.optimizer,
                       "data": "synthetic" if not args.cpu else "stub (CPU / gloo run of the rank logic)"}))
 if world > 1:
     dist.destroy_process_group()
