@@ -403,6 +403,40 @@ int ssdk_fuse(const ssdk_fuse_desc* desc, void* stream);
 int ssdk_preprocess(const void* x, int src_dtype, int src_layout, int N, int H, int W, int C, const float* mean,
                     const float* std, void* y, int dst_dtype, void* stream);
 
+/* Training input pipeline (the DALI graph of ssds/dataset/dali_dataiterator.py:72-103 as ONE pass; csrc/ssdk_augment.hip,
+ * DESIGN.md "Data input"): SSD crop -> colour twist -> horizontal flip -> paste onto a filled canvas -> bilinear resize to
+ * H x W -> `(v - mean) / std` -> cast, NCHW.  The host draws every random number (ssds/dataset/augment.py) and describes
+ * each image of the batch with one descriptor; a kernel lane maps its output pixels back to four source taps.
+ *   pixels      DEVICE, packed uint8 HWC RGB images of different sizes, pixels_bytes long
+ *   descs_host  HOST array [B].  Every descriptor is checked before anything is launched: the image inside pixels_bytes,
+ *               the crop inside the image, the pasted crop inside the canvas (canvas sides <= 32768), sizes >= 1, flip
+ *               0 | 1, color / fill finite.  A bad one is SSDK_E_BADARG with a message naming the field and NO launch
+ *               (so is a null pointer, B outside [1, 65535], H | W outside [1, 16384], another dst_dtype, a short
+ *               workspace).  The checked array goes to `workspace` with one async copy on `stream`; keep it alive (and
+ *               unchanged) until that copy has run if it is pinned memory.
+ *   color       row-major 3x4 applied to (r, g, b, 1) of a source pixel, result clamped to [0, 255] (not rounded);
+ *   fill        the canvas outside the pasted crop (not colour-twisted)
+ *   mean, std   HOST fp32 [3];  y  DEVICE [B,3,H,W] of dst_dtype (SSDK_F32 | SSDK_BF16 | SSDK_F16)
+ *   workspace   DEVICE, ssdk_augment_workspace_bytes(B) bytes (0 for a B out of range)
+ * Resize: bilinear, half-pixel centres, edge-clamped, no antialiasing; source coordinate of output column x =
+ * ((2x+1) * canvas_w - W) / (2W), integer part and remainder in integer arithmetic, weight = remainder / (2W) in fp32.
+ * An eager call (its descriptors change with every batch): not meant for hipGraph capture.  The descriptor is not part
+ * of ssdk_struct_size(): ssdk_augment_desc_bytes() reports its size. */
+typedef struct ssdk_augment_desc {
+  int64_t src_offset; /* first byte of the image in `pixels`; rows are src_w * 3 bytes */
+  int32_t src_h, src_w;
+  int32_t crop_x, crop_y, crop_w, crop_h;
+  int32_t canvas_w, canvas_h, paste_x, paste_y;
+  int32_t flip;
+  float color[12]; /* row-major 3x4, applied to (r, g, b, 1) */
+  float fill[3];
+} ssdk_augment_desc;
+size_t ssdk_augment_desc_bytes(void);
+size_t ssdk_augment_workspace_bytes(int B);
+int ssdk_augment(const void* pixels, size_t pixels_bytes, const ssdk_augment_desc* descs_host, int B, int H, int W,
+                 const float* mean, const float* std, void* y, int dst_dtype, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
 /* Dense 1x1 / stride-1 convolutions of the TRAINING step on NCHW tensors (version 240; csrc/ssdk_pwtrain.hip): the pointwise
  * convolutions of MobileNetV2's inverted-residual blocks (nets/mobilenet.py:56, 78 through torchvision's InvertedResidual /
  * ConvBNReLU) and of the SSD extras (layers/basic_layers.py:40-57), forward and backward in the reference's DDP step

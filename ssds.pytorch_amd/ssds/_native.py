@@ -86,6 +86,13 @@ class XpairDesc(ctypes.Structure):
         ("w1_frag", ctypes.c_void_p), ("w2_frag", ctypes.c_void_p)]
 
 
+class AugmentDesc(ctypes.Structure):
+    """ssdk_augment_desc: one image of an ssdk_augment batch (ssds/dataset/augment.py DESC_DTYPE is the numpy view of it)."""
+    _fields_ = [("src_offset", ctypes.c_int64)] + [(n, ctypes.c_int32) for n in (
+        "src_h", "src_w", "crop_x", "crop_y", "crop_w", "crop_h", "canvas_w", "canvas_h", "paste_x", "paste_y", "flip")] + [
+        ("color", ctypes.c_float * 12), ("fill", ctypes.c_float * 3)]
+
+
 class Op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("lane", ctypes.c_int32), ("conv", ConvDesc), ("mb", MbConvDesc),
                 ("fuse", FuseDesc), ("stem", StemDesc), ("pool", PoolDesc), ("xpair", XpairDesc)]
@@ -277,6 +284,17 @@ def _load():
     lib.ssdk_conv_sequence.argtypes = [c.POINTER(ConvDesc), i32, vp, sz, vp]
     lib.ssdk_conv_sequence.restype = i32
     lib.ssdk_mbconv.argtypes = [c.POINTER(MbConvDesc), vp]
+    # ssdk_augment_desc is not behind ssdk_struct_size (its indices are part of ABI 245): the library reports its size itself
+    lib.ssdk_augment_desc_bytes.restype = sz
+    lib.ssdk_augment_desc_bytes.argtypes = []
+    if int(lib.ssdk_augment_desc_bytes()) != c.sizeof(AugmentDesc):
+        raise ImportError("libssdk.so at {} has sizeof(ssdk_augment_desc) = {} but ssds/_native.py mirrors it with {} bytes: "
+                          "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, int(lib.ssdk_augment_desc_bytes()),
+                                                                               c.sizeof(AugmentDesc)))
+    lib.ssdk_augment_workspace_bytes.restype = sz
+    lib.ssdk_augment_workspace_bytes.argtypes = [i32]
+    lib.ssdk_augment.argtypes = [vp, sz, c.POINTER(AugmentDesc), i32, i32, i32, c.POINTER(f32), c.POINTER(f32), vp, i32, vp, sz, vp]
+    lib.ssdk_augment.restype = i32
     lib.ssdk_mbconv.restype = i32
     lib.ssdk_xpair.argtypes = [c.POINTER(XpairDesc), vp]
     lib.ssdk_xpair.restype = i32
@@ -300,7 +318,7 @@ EXPORTS = ("ssdk_version", "ssdk_struct_size", "ssdk_abi_check", "ssdk_last_erro
            "ssdk_ctx_create", "ssdk_ctx_destroy", "ssdk_ctx_set_tail_stream", "ssdk_ctx_set_side_lane", "ssdk_ctx_set_profiling",
            "ssdk_ctx_get_timings", "ssdk_ctx_set_op_profiling", "ssdk_ctx_get_op_timings", "ssdk_ctx_get_tail_stamps",
            "ssdk_run_ops_ctx", "ssdk_decode_nms_ctx",
-           "ssdk_weight_frag_bytes", "ssdk_conv_workspace_bytes", "ssdk_conv", "ssdk_conv_sequence", "ssdk_mbconv", "ssdk_mbk_image_bytes", "ssdk_xpair", "ssdk_fuse", "ssdk_preprocess", "ssdk_dwconv_fwd_stats_workspace_bytes", "ssdk_dwconv_fwd_stats", "ssdk_dwconv_affine_supported", "ssdk_dwconv_fwd_affine", "ssdk_dwconv_bwd_weight_affine", "ssdk_bn_act_train_stats", "ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_stats_workspace_bytes", "ssdk_pw_forward_stats", "ssdk_bn_act_train_fwd_sums", "ssdk_pw_wgrad_workspace_bytes", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3", "ssdk_im2col3x3_folded", "ssdk_col2im3x3_folded", "ssdk_stem3x3s2_wgrad_workspace_bytes", "ssdk_stem3x3s2_fwd", "ssdk_stem3x3s2_wgrad", "ssdk_pack_conv3x3", "ssdk_pack_conv3x3_dgrad", "ssdk_concat_nchw_to_nhwc", "ssdk_sgd_step", "ssdk_adam_step", "ssdk_rmsprop_step", "ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data",
+           "ssdk_weight_frag_bytes", "ssdk_conv_workspace_bytes", "ssdk_conv", "ssdk_conv_sequence", "ssdk_mbconv", "ssdk_mbk_image_bytes", "ssdk_xpair", "ssdk_fuse", "ssdk_preprocess", "ssdk_augment_desc_bytes", "ssdk_augment_workspace_bytes", "ssdk_augment", "ssdk_dwconv_fwd_stats_workspace_bytes", "ssdk_dwconv_fwd_stats", "ssdk_dwconv_affine_supported", "ssdk_dwconv_fwd_affine", "ssdk_dwconv_bwd_weight_affine", "ssdk_bn_act_train_stats", "ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_stats_workspace_bytes", "ssdk_pw_forward_stats", "ssdk_bn_act_train_fwd_sums", "ssdk_pw_wgrad_workspace_bytes", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3", "ssdk_im2col3x3_folded", "ssdk_col2im3x3_folded", "ssdk_stem3x3s2_wgrad_workspace_bytes", "ssdk_stem3x3s2_fwd", "ssdk_stem3x3s2_wgrad", "ssdk_pack_conv3x3", "ssdk_pack_conv3x3_dgrad", "ssdk_concat_nchw_to_nhwc", "ssdk_sgd_step", "ssdk_adam_step", "ssdk_rmsprop_step", "ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data",
            "ssdk_dwconv_bwd_weight_workspace_bytes", "ssdk_dwconv_bwd_weight", "ssdk_dwconv_plan", "ssdk_bn_workspace_bytes",
            "ssdk_bn_train_fwd", "ssdk_bn_train_bwd", "ssdk_bn_act_train_fwd", "ssdk_bn_act_train_bwd", "ssdk_bn_sync_local_stats",
            "ssdk_bn_sync_fwd_finalize", "ssdk_bn_act_apply", "ssdk_bn_sync_bwd_local", "ssdk_bn_sync_bwd_apply", "ssdk_conv_stem7", "ssdk_maxpool3x3s2", "ssdk_run_ops", "ssdk_conv_bn_act", "ssdk_set_profiling", "ssdk_get_timings")
