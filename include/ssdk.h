@@ -281,6 +281,13 @@ int ssdk_map_average_precision(const unsigned char* tp_sorted, const long long* 
  *   y = act(conv(x, w) * scale[c] + bias[c]) (+ residual)
  * Dispatch:  groups == 1, Cin % 8 == 0  -> MFMA implicit GEMM (1x1 / 3x3, stride 1|2, pad k/2)
  *            groups == Cin == Cout      -> depthwise 3x3 (HBM-bound, NHWC)
+ *            1 < groups < Cin, Cin == Cout, k == 3 (RegNetX / ResNeXt bottlenecks), gw = Cin / groups channels per group:
+ *              gw == 16                           -> gconv3x3_g16[_tile]_kernel, reads `w`
+ *              gw == 4 (groups even), 8, 24, 32, ... 256 (any multiple of 8)
+ *                                                 -> gconv3x3_any_kernel: the kernel reads its weights from `w_frag` = the
+ *                                                    grouped image below (SSDK_E_BADARG when it is NULL); `w` (KRSC) must
+ *                                                    still be passed, non-NULL and 16-byte aligned, as for every kind;
+ *                                                    NHWC in / out, scale required
  *            Cin <= 4 (image stem)      -> direct 3x3; w is fp32 with the BN scale folded in, scale = NULL
  * Layouts:   x NHWC (= torch channels_last) except the stem which also takes NCHW;
  *            w KRSC [Cout][kh][kw][Cin/groups] in the activation dtype;  scale (may be NULL = 1), bias fp32;
@@ -296,7 +303,7 @@ typedef struct ssdk_conv_desc {
   const void* residual; /* optional, NHWC: y = act(conv) + residual, or act(conv + residual) with res_mode bit 1 */
   void* y;
   void* y2;             /* optional second output (NCHW split) */
-  int32_t N, Cin, H, W, Cout, k, stride, groups; /* groups: 1 dense | Cin depthwise (k=3) | Cin/16 grouped (k=3) */
+  int32_t N, Cin, H, W, Cout, k, stride, groups; /* groups: 1 dense | Cin depthwise (k=3) | grouped (k=3, Cin == Cout): any supported width, see Dispatch */
   int32_t act, act2, split;
   int32_t dtype;        /* SSDK_BF16 | SSDK_F16 (input, weights and output) */
   int32_t in_layout, out_layout;
@@ -307,6 +314,14 @@ typedef struct ssdk_conv_desc {
                            traffic) read it instead of `w`: 1 KiB contiguous per wave instruction instead of 16 rows x 64 B,
                            measured 40-50 instead of 14 B/clk per CU (tools/micro/wstream.hip) */
 } ssdk_conv_desc;
+/* Grouped image (w_frag of a grouped 3x3 layer whose width gw is not 16), a special case of the fragment-major image defined
+ * next: per group a matrix [RB * 16][Kpad], RB = ceil(gw / 16),
+ * Kpad = 32 * ceil(9 * gw / 32), row = output channel inside the group, k = tap * gw + ci (tap = 3 * ky + kx, ci = input channel
+ * inside the group), zeros in rows >= gw and columns >= 9 * gw; the groups concatenated along the rows.  The image is the
+ * fragment-major image (above) of that [groups * RB * 16][Kpad] matrix, so ssdk_weight_frag_bytes(groups * RB * 16, Kpad) is its
+ * size.  gw == 4: neighbouring pairs of groups are first merged into block-diagonal groups of 8 (output channel j of a pair
+ * reads input channels 4 * (j / 4) .. + 3 of the pair, zeros elsewhere), i.e. the image is that of groups / 2 groups of 8; the
+ * descriptor keeps the model's `groups`.  The Python host builds it in fused_conv.pack_grouped_frag (ConvPack.gfrag()). */
 /* Fragment-major image of a row-major weight matrix w[rows][K] (a KRSC conv weight: rows = Cout, K = k*k*Cin), K % 32 == 0:
  *   frag[g][ks][fg][fr][j] = w[16*g + fr][32*ks + 8*fg + j]     g < ceil(rows/16), ks < K/32, fg < 4, fr < 16, j < 8
  * rows past `rows` are zero.  One (g, ks) block = 1 KiB = the A operand of one v_mfma_f32_16x16x32 k-step of 16 output

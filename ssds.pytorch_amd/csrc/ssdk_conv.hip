@@ -1139,10 +1139,13 @@ extern "C" int ssdk_conv(const ssdk_conv_desc* d, void* workspace, size_t worksp
     }
     return check_launch("dwconv3x3_kernel");
   }
-  if (d->groups != 1) {  // grouped: 16 channels per group (RegNetX bottlenecks)
+  if (d->groups != 1) {  // grouped 3x3 (RegNetX / ResNeXt bottlenecks): 16 channels per group on its own kernels, other widths on one
     if (d->groups * 16 == d->Cin && d->Cin == d->Cout) return launch_gconv3x3_g16(d, Ho, Wo, stream);
-    set_error("conv: groups must be 1 (dense), Cin (depthwise) or Cin/16 (16-channel groups); got %d for Cin=%d",
-              d->groups, d->Cin);
+    const int gw = d->groups > 0 && d->Cin % d->groups == 0 ? d->Cin / d->groups : 0;
+    if (d->Cin == d->Cout && ((gw >= 8 && gw <= 256 && gw % 8 == 0) || (gw == 4 && d->groups % 2 == 0)))
+      return launch_gconv3x3_any(d, Ho, Wo, stream);
+    set_error("conv: groups must be 1 (dense), Cin (depthwise) or leave Cin == Cout with 4 (an even number of groups), 8, 16, "
+              "24, ... 256 channels per group; got %d for Cin=%d Cout=%d", d->groups, d->Cin, d->Cout);
     return SSDK_E_BADARG;
   }
   if (d->Cin <= 4) {  // stem: w is fp32 [Cout][3][3][Cin] with the BN scale folded in

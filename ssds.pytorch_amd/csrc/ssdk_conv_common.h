@@ -175,6 +175,9 @@ __device__ __forceinline__ void glds16(const void* g, unsigned char* l) {
 
 // grouped 3x3 convolution, 16 channels per group (ssdk_gconv.hip)
 int launch_gconv3x3_g16(const ssdk_conv_desc* d, int Ho, int Wo, hipStream_t stream);
+// grouped 3x3 convolution, any other supported width: 4 or a multiple of 8 up to 256 channels per group; reads d->w_frag
+// (ssdk_gconv_any.hip)
+int launch_gconv3x3_any(const ssdk_conv_desc* d, int Ho, int Wo, hipStream_t stream);
 
 // halo-tile 3x3 kernel with split-K over its channel slabs: slices to use (1: no split) and the workspace they need
 int halo_splitk_plan(int N, int Cin, int Ho, int Wo, int Cout, bool nchw, size_t* ws_bytes);

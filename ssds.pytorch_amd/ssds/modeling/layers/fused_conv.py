@@ -59,8 +59,14 @@ def fold_bn(conv, bn):
     return scale.contiguous(), bias.contiguous()
 
 
+# SSDK_GCONV_ANY=0: grouped 3x3 layers whose width is not 16 are "not covered" again, so their backbone runs on
+# PyTorch-ROCm as it did before csrc/ssdk_gconv_any.hip existed (A/B measurements only; docs/SWITCHES.md).
+USE_GCONV_ANY = os.environ.get("SSDK_GCONV_ANY", "1") != "0"
+GCONV_ANY_MAX_WIDTH = 256  # channels per group (csrc/ssdk_gconv_any.hip launch_gconv3x3_any)
+
+
 def conv_kind(conv):
-    """'dense' | 'dw' | 'g16' | 'stem' | None (None: not covered by the HIP kernels -> torch, reported)."""
+    """'dense' | 'dw' | 'g16' | 'gany' | 'stem' | None (None: not covered by the HIP kernels -> torch, reported)."""
     k = conv.kernel_size
     if not (k[0] == k[1] and k[0] in (1, 3) and conv.stride[0] == conv.stride[1] and conv.stride[0] in (1, 2)
             and conv.padding == (k[0] // 2, k[0] // 2) and conv.dilation == (1, 1)
@@ -74,7 +80,40 @@ def conv_kind(conv):
         return "dw"
     if conv.in_channels == conv.out_channels == conv.groups * 16 and k[0] == 3:
         return "g16"  # 16 channels per group (RegNetX bottlenecks): csrc/ssdk_gconv.hip
+    if conv.in_channels == conv.out_channels and k[0] == 3 and conv.in_channels % conv.groups == 0 and USE_GCONV_ANY:
+        gw = conv.in_channels // conv.groups
+        if (gw % 8 == 0 and gw <= GCONV_ANY_MAX_WIDTH) or (gw == 4 and conv.groups % 2 == 0):
+            return "gany"  # any other width (RegNetX, ResNeXt): csrc/ssdk_gconv_any.hip, reads the grouped image
     return None
+
+
+def pack_grouped_frag(w, groups):
+    """Fragment-major image of the weights of a grouped 3x3 convolution for csrc/ssdk_gconv_any.hip (include/ssdk.h, "grouped
+    image").  ``w``: KRSC [C][3][3][gw], gw = C / groups channels per group.  Pure layout, on the tensor's own device (CPU
+    tensors too) -> (image [groups' * RB][KS][4][16][8], groups', gw'):
+
+    * gw == 4 (ResNeXt50 layer1): neighbouring pairs of groups are merged into block-diagonal groups of gw' = 8 -- output
+      channel j of a pair reads input channels 4 (j // 4) .. + 3 of the pair's 8, the other 4 slots are zeros.  The added
+      products are exact zeros in an fp32 accumulator, so for finite inputs no result changes.  Otherwise gw' = gw.
+    * per group a [RB * 16][Kpad] matrix: row = output channel of the group, k = tap * gw' + ci (tap = 3 ky + kx),
+      RB = ceil(gw' / 16), Kpad = 32 * ceil(9 gw' / 32) = 32 KS, zeros in the padding rows and columns;
+    * the groups concatenated along the rows, and that [groups' * RB * 16][Kpad] matrix in fragment-major order:
+      element (row, k) at [row // 16][k // 32][(k % 32) // 8][row % 16][k % 8]."""
+    c, kh, kw, gw = (int(v) for v in w.shape)
+    assert kh == 3 and kw == 3 and c == groups * gw, (tuple(w.shape), groups)
+    if gw == 4:
+        assert groups % 2 == 0, groups
+        wide = w.new_zeros((c // 8, 2, 4, 3, 3, 2, 4))
+        src = w.reshape(c // 8, 2, 4, 3, 3, 4)
+        wide[:, 0, :, :, :, 0] = src[:, 0]
+        wide[:, 1, :, :, :, 1] = src[:, 1]
+        w, groups, gw = wide.reshape(c, 3, 3, 8), groups // 2, 8
+    assert gw % 8 == 0, gw
+    rb, ks = (gw + 15) // 16, (9 * gw + 31) // 32
+    mat = w.new_zeros((groups, rb * 16, ks * 32))
+    mat[:, :gw, :9 * gw] = w.reshape(groups, gw, 9 * gw)
+    img = mat.view(groups * rb, 16, ks, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+    return img, groups, gw
 
 
 # Fragment-major weight images for the kernels that stream weights into operand registers (ConvPack.frag); False keeps
@@ -108,6 +147,18 @@ class ConvPack(object):
         self._frag = ((self.w.data_ptr(), self.w._version), img)
         return img
 
+    def gfrag(self):
+        """Grouped image of a 'gany' layer (pack_grouped_frag): the ONLY weight tensor its kernel reads, so it is built whatever
+        USE_WFRAG says.  Cached like frag(); the pack, which every plan keeps, keeps the image alive."""
+        assert self.kind == "gany", self.kind
+        cached = getattr(self, "_frag", None)
+        if cached is not None and cached[0] == (self.w.data_ptr(), self.w._version):
+            return cached[1]
+        img, groups, gw = pack_grouped_frag(self.w, self.groups)
+        assert img.numel() * 2 == N.lib.ssdk_weight_frag_bytes(groups * ((gw + 15) // 16) * 16, 32 * ((9 * gw + 31) // 32))
+        self._frag = ((self.w.data_ptr(), self.w._version), img)
+        return img
+
     def __init__(self, conv, bn, act, dtype, extra_cout=None):
         self._frag = None
         self.kind = conv_kind(conv)
@@ -125,7 +176,8 @@ class ConvPack(object):
             self.scale = scale
         else:  # [Cout,Cin,kh,kw] -> [Cout][kh][kw][Cin]
             self.w = w.permute(0, 2, 3, 1).contiguous().to(dtype)
-            self.scale = scale if bn is not None else None
+            # (the grouped kernels have no scale-free form: a layer without BatchNorm passes fold_bn's vector of ones)
+            self.scale = scale if bn is not None or self.kind in ("g16", "gany") else None
         self.bias = bias
 
 
@@ -486,7 +538,10 @@ def wants_frag(pack, h, w, has_residual, in_layout=N.NHWC):
 def fill_desc(d, x_ptr, n, h, w, pack, dtype_code, act, y_ptr, in_layout=N.NHWC, out_layout=N.NHWC,
               residual_ptr=None, y2_ptr=None, split=None, act2=None):
     d.x, d.w = x_ptr, pack.w.data_ptr()
-    frag = pack.frag() if wants_frag(pack, h, w, residual_ptr is not None, in_layout) else None
+    if pack.kind == "gany":  # not optional: gconv3x3_any_kernel reads nothing else
+        frag = pack.gfrag()
+    else:
+        frag = pack.frag() if wants_frag(pack, h, w, residual_ptr is not None, in_layout) else None
     d.w_frag = frag.data_ptr() if frag is not None else None
     d.scale = pack.scale.data_ptr() if pack.scale is not None else None
     d.bias = pack.bias.data_ptr()

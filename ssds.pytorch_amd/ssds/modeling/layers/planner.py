@@ -188,7 +188,7 @@ def record_resnet(plan, val, net):
                 idt = plan.conv(cur, _pack(dconv, dbn, "none", dt))
             if isinstance(blk, Bottleneck):
                 o1 = plan.conv(cur, _pack(blk.conv1, blk.bn1, "relu", dt))
-                o2 = plan.conv(o1, _pack(blk.conv2, blk.bn2, "relu", dt))
+                o2 = plan.conv(o1, _pack(blk.conv2, blk.bn2, "relu", dt, kinds=("dense", "g16", "gany")))  # (ResNeXt: grouped)
                 plan.release(o1)
                 out = plan.conv(o2, _pack(blk.conv3, blk.bn3, "relu", dt), residual=idt, res_mode=2)
                 plan.release(o2)
@@ -209,7 +209,7 @@ def record_resnet(plan, val, net):
 
 
 def record_regnet(plan, val, net):
-    """RegNetX (nets/regnet.py): 3x3/s2 stem, then bottleneck blocks 1x1 -> grouped 3x3 (16 channels per group,
+    """RegNetX (nets/regnet.py): 3x3/s2 stem, then bottleneck blocks 1x1 -> grouped 3x3 (any supported group width,
     stride s) -> 1x1 whose last conv adds the (projected) skip and applies the ReLU in its epilogue."""
     from ssds.modeling.nets.regnet import RegNet
 
@@ -229,7 +229,7 @@ def record_regnet(plan, val, net):
                 skip = plan.conv(cur, _pack(blk.proj, blk.bn, "none", dt))
             f = blk.f
             a = plan.conv(cur, _pack(f.a, f.a_bn, "relu", dt))
-            b = plan.conv(a, _pack(f.b, f.b_bn, "relu", dt, kinds=("g16", "dense")))
+            b = plan.conv(a, _pack(f.b, f.b_bn, "relu", dt, kinds=("g16", "gany", "dense")))
             plan.release(a)
             out = plan.conv(b, _pack(f.c, f.c_bn, "relu", dt), residual=skip, res_mode=2)
             plan.release(b)
