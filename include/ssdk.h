@@ -505,6 +505,30 @@ int ssdk_stem3x3s2_fwd(const void* x, const float* w, void* y, int N, int Cin, i
 int ssdk_stem3x3s2_wgrad(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int H, int W,
                          int Cout, int dtype, void* stream);
 
+/* The grouped 3x3 convolution of the TRAINING step (RegNetX / ResNeXt bottlenecks: nets/regnet.py, nets/resnet.py; csrc/ssdk_gconvtrain.hip):
+ * pad 1, stride 1 | 2, C == groups * gw input and output channels, gw = 4 (an even number of groups) or a multiple of 8 up to 256
+ * (16 included).  16-bit tensors (SSDK_BF16 | SSDK_F16), NCHW contiguous in and out, 2-byte aligned; fp32 accumulation; no BatchNorm
+ * fold, no activation.  H, W are always the LAYER INPUT's size, Ho = (H - 1) / stride + 1.
+ *   ssdk_gconv3x3_train_prepare   w32 [C, gw, 3, 3] fp32 master weights -> w_fwd and / or w_dgrad (either may be NULL), two grouped
+ *                                 images (above) in `dtype`, 16-byte aligned, ssdk_weight_frag_bytes(groups' * RB * 16, Kpad) bytes
+ *                                 each: w_fwd of the weights themselves (fused_conv.pack_grouped_frag of the cast tensor, bit for
+ *                                 bit), w_dgrad of W'[g][ci][ky][kx][co] = W[g][co][2 - ky][2 - kx][ci] (per group transposed, taps
+ *                                 flipped: groupedconv.pack_grouped_frag_dgrad).  Replaces autocast's cast of the parameter.
+ *   ssdk_gconv3x3_train_forward   y [N, C, Ho, Wo] = conv(x [N, C, H, W], w_fwd)
+ *   ssdk_gconv3x3_train_dgrad     dx [N, C, H, W] = conv^T(dy [N, C, Ho, Wo], w_dgrad); stride 2 is a transposed convolution by
+ *                                 input-pixel parity (9 taps per 2 x 2 input pixels), not a convolution over a zero-dilated dy
+ *   ssdk_gconv3x3_train_wgrad     dw [C, gw, 3, 3] fp32 = sum over pixels dy x; fp32 partial tiles of pixel ranges through `workspace`
+ *                                 (ssdk_gconv3x3_train_wgrad_workspace_bytes, 16-byte aligned), added in index order: bit-reproducible,
+ *                                 no atomics.  The workspace query returns 0 for a shape the kernels do not take. */
+int ssdk_gconv3x3_train_prepare(const float* w32, void* w_fwd, void* w_dgrad, int C, int groups, int dtype, void* stream);
+int ssdk_gconv3x3_train_forward(const void* x, const void* w_fwd, void* y, int N, int C, int H, int W, int groups, int stride, int dtype,
+                                void* stream);
+int ssdk_gconv3x3_train_dgrad(const void* dy, const void* w_dgrad, void* dx, int N, int C, int H, int W, int groups, int stride, int dtype,
+                              void* stream);
+size_t ssdk_gconv3x3_train_wgrad_workspace_bytes(int N, int C, int H, int W, int groups, int stride);
+int ssdk_gconv3x3_train_wgrad(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int C, int H, int W,
+                              int groups, int stride, int dtype, void* stream);
+
 /* Weights of a 3x3 layer -- or of the loc | conf PAIR of an SSD level (reference ssd.py:100-103), w2 / b2 / n2 = NULL / NULL / 0
  * for a single layer -- from the fp32 master tensors [n, Cin, 3, 3] into the layouts ssdk_conv reads, in one launch (the head
  * convolutions of the TRAINING step run on the inference kernels: weights change every step): krsc = 16-bit [n1 + n2][3][3][Cin];

@@ -1,0 +1,177 @@
+"""Grouped 3x3 convolutions of the training step on the NCHW tensors themselves (csrc/ssdk_gconvtrain.hip): the bottleneck
+3x3 of RegNetX (nets/regnet.py) and ResNeXt (nets/resnet.py), forward, input gradient and weight gradient.
+
+PyTorch-ROCm sends a grouped ``nn.Conv2d`` in bf16 to MIOpen's grouped convolution, through autocast's cast of the weight.
+``GroupedConv3x3`` is an ``nn.Conv2d`` (same parameters, ``state_dict`` keys and initialisation) whose 16-bit HIP-device
+forward / backward run on the ssdk kernels:
+
+    prepare          ssdk_gconv3x3_train_prepare   fp32 master weight -> the 16-bit forward and input-gradient images
+    forward          ssdk_gconv3x3_train_forward   y  = conv(x, W)
+    input gradient   ssdk_gconv3x3_train_dgrad     dx = conv^T(dy, W)   (stride 2: by input-pixel parity, no zero-dilated dy)
+    weight gradient  ssdk_gconv3x3_train_wgrad     dW fp32, pixel ranges added in index order: bit-reproducible
+
+pad 1, stride 1 | 2, Cin == Cout == groups * gw with gw = 4 (an even number of groups) or a multiple of 8 up to 256.  CPU
+tensors, fp32 tensors, non-contiguous tensors and every other layer shape take ``nn.Conv2d.forward``."""
+import os
+
+import torch
+import torch.nn as nn
+
+from ssds import _native as N
+from ssds.modeling.layers.fused_conv import pack_grouped_frag
+
+MAX_WIDTH = 256  # channels per group (csrc/ssdk_gconvtrain.hip gt_shape)
+STATS = {"swapped": 0, "native_forward": 0, "native_dgrad": 0, "native_wgrad": 0}
+
+
+def width_supported(channels, groups):
+    """The widths csrc/ssdk_gconvtrain.hip takes: 4 channels per group with an even number of groups, or a multiple of 8 up
+    to 256."""
+    if groups < 1 or channels % groups:
+        return False
+    gw = channels // groups
+    return (gw == 4 and groups % 2 == 0) or (gw % 8 == 0 and 8 <= gw <= MAX_WIDTH)
+
+
+def supported(m):
+    """``m`` is a grouped (neither dense nor depthwise) 3x3 / pad 1 / stride 1 | 2 convolution of a supported width."""
+    return (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.padding == (1, 1) and m.dilation == (1, 1)
+            and m.stride in ((1, 1), (2, 2)) and m.padding_mode == "zeros" and m.in_channels == m.out_channels
+            and 1 < m.groups < m.in_channels and width_supported(m.in_channels, m.groups))
+
+
+def image_shape(channels, groups):
+    """-> (groups', gw', RB, KS) of the grouped image (include/ssdk.h): 4-wide groups merged into pairs."""
+    gw = channels // groups
+    if gw == 4:
+        groups, gw = groups // 2, 8
+    return groups, gw, (gw + 15) // 16, (9 * gw + 31) // 32
+
+
+def pack_grouped_frag_dgrad(w, groups):
+    """The grouped image of the INPUT-GRADIENT weights of a grouped 3x3 convolution: ``w`` KRSC [C][3][3][gw] as for
+    fused_conv.pack_grouped_frag; per group the matrix is transposed (rows = input channels, k = tap' * gw + co) and the taps
+    are flipped, W'[g][ci][ky][kx][co] = W[g][co][2 - ky][2 - kx][ci], so that at stride 1 dx = conv(dy, W'), pad 1.  Pure
+    layout, on the tensor's own device (CPU tensors too) -> (image, groups', gw') as pack_grouped_frag (4-wide groups merged)."""
+    c, kh, kw, gw = (int(v) for v in w.shape)
+    assert kh == 3 and kw == 3 and c == groups * gw, (tuple(w.shape), groups)
+    wt = w.reshape(groups, gw, 3, 3, gw).flip(2, 3).permute(0, 4, 2, 3, 1).reshape(c, 3, 3, gw)
+    return pack_grouped_frag(wt.contiguous(), groups)
+
+
+def unpack_grouped_frag(img, groups, gw):
+    """The layout of include/ssdk.h read backwards: image [groups * RB][KS][4][16][8] -> OIHW weights [groups * gw][gw][3][3]
+    of a convolution with ``groups`` groups (the merged groups of a 4-wide layer come back as block-diagonal groups of 8)."""
+    rb, ks = (gw + 15) // 16, (9 * gw + 31) // 32
+    assert tuple(img.shape) == (groups * rb, ks, 4, 16, 8), tuple(img.shape)
+    mat = img.permute(0, 3, 1, 2, 4).reshape(groups, rb * 16, ks * 32)
+    w = mat[:, :gw, :9 * gw].reshape(groups, gw, 3, 3, gw)  # k = tap * gw + ci
+    return w.permute(0, 1, 4, 2, 3).reshape(groups * gw, gw, 3, 3).contiguous()
+
+
+def prepare_images(weight, groups, dtype, want_dgrad=True):
+    """fp32 (or 16-bit) weight [C, gw, 3, 3] on a HIP device -> (forward image, input-gradient image | None) in ``dtype``, one
+    launch."""
+    c = int(weight.shape[0])
+    ge, gwe, rb, ks = image_shape(c, groups)
+    dev = weight.device
+    w32 = weight.detach().float().contiguous()  # (a 16-bit weight survives the round trip exactly)
+    fwd = torch.empty((ge * rb, ks, 4, 16, 8), device=dev, dtype=dtype)
+    dg = torch.empty_like(fwd) if want_dgrad else None
+    with torch.cuda.device(dev):
+        N.check(N.lib.ssdk_gconv3x3_train_prepare(w32.data_ptr(), fwd.data_ptr(), None if dg is None else dg.data_ptr(), c, groups,
+                                                  N.dtype_code(fwd), N.stream_ptr(dev)), "gconv3x3_train_prepare")
+    return fwd, dg
+
+
+class _GroupedConv3x3(torch.autograd.Function):
+    """x [N, C, H, W] 16 bit, contiguous; weight [C, gw, 3, 3] fp32 (the master parameter under autocast: the weight gradient
+    comes back in fp32) or in x's dtype; bias or None (added and reduced on torch: no registered backbone has one)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, groups):
+        n, c, h, wd = (int(v) for v in x.shape)
+        dev, dt = x.device, x.dtype
+        ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
+        code = N.dtype_code(x)
+        x = x.detach()
+        fwd, dg = prepare_images(weight, groups, dt, want_dgrad=ctx.needs_input_grad[0])
+        y = torch.empty((n, c, ho, wo), device=dev, dtype=dt)
+        with torch.cuda.device(dev):
+            N.check(N.lib.ssdk_gconv3x3_train_forward(x.data_ptr(), fwd.data_ptr(), y.data_ptr(), n, c, h, wd, groups, stride, code,
+                                                      N.stream_ptr(dev)), "gconv3x3_train_forward")
+        STATS["native_forward"] += 1
+        if bias is not None:
+            y += bias.detach().to(dt).view(1, c, 1, 1)
+        ctx.save_for_backward(x, dg)
+        ctx.meta = (weight.dtype, None if bias is None else bias.dtype, stride, groups)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, dg = ctx.saved_tensors
+        wdt, bdt, stride, groups = ctx.meta
+        n, c, h, wd = (int(v) for v in x.shape)
+        dev, dt = x.device, x.dtype
+        gy = gy.contiguous()
+        if gy.dtype != dt:
+            gy = gy.to(dt)
+        code = N.dtype_code(x)
+        gx = gw = gb = None
+        with torch.cuda.device(dev):
+            sp = N.stream_ptr(dev)
+            if ctx.needs_input_grad[0]:
+                gx = torch.empty_like(x)
+                N.check(N.lib.ssdk_gconv3x3_train_dgrad(gy.data_ptr(), dg.data_ptr(), gx.data_ptr(), n, c, h, wd, groups, stride, code, sp),
+                        "gconv3x3_train_dgrad")
+                STATS["native_dgrad"] += 1
+            if ctx.needs_input_grad[1]:
+                need = int(N.lib.ssdk_gconv3x3_train_wgrad_workspace_bytes(n, c, h, wd, groups, stride))
+                ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+                gw32 = torch.empty((c, c // groups, 3, 3), device=dev, dtype=torch.float32)
+                N.check(N.lib.ssdk_gconv3x3_train_wgrad(x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), (ws.data_ptr() + 15) & ~15, need,
+                                                        n, c, h, wd, groups, stride, code, sp), "gconv3x3_train_wgrad")
+                STATS["native_wgrad"] += 1
+                gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
+        if bdt is not None and ctx.needs_input_grad[2]:
+            gb = gy.sum((0, 2, 3), dtype=torch.float32).to(bdt)
+        return gx, gw, gb, None, None
+
+
+def grouped_conv3x3(x, weight, bias=None, stride=1, groups=1):
+    """The native path, called explicitly: x 16-bit contiguous NCHW on a HIP device; differentiable."""
+    return _GroupedConv3x3.apply(x, weight, bias, stride, groups)
+
+
+class GroupedConv3x3(nn.Conv2d):
+    """``nn.Conv2d(C, C, 3, stride 1 | 2, pad 1, groups)`` whose 16-bit HIP-device forward / backward run on
+    csrc/ssdk_gconvtrain.hip (same parameters, ``state_dict`` keys and initialisation); everything else is ``nn.Conv2d.forward``."""
+
+    def _native(self, x):
+        return x.is_cuda and x.dim() == 4 and x.is_contiguous() and int(x.shape[1]) == self.in_channels and supported(self)
+
+    def forward(self, x):
+        if not self._native(x):
+            return super(GroupedConv3x3, self).forward(x)
+        w = self.weight
+        if torch.is_autocast_enabled():
+            x = x.to(torch.get_autocast_dtype("cuda"))
+        if x.dtype not in (torch.bfloat16, torch.float16) or (w.dtype != torch.float32 and w.dtype != x.dtype):
+            return super(GroupedConv3x3, self).forward(x)
+        with torch.autocast("cuda", enabled=False):
+            return _GroupedConv3x3.apply(x, w, self.bias, self.stride[0], self.groups)
+
+
+def enabled():
+    """SSDK_GCONV_TRAIN (default 1; docs/SWITCHES.md): 0 leaves the grouped 3x3 layers of the training step on nn.Conv2d."""
+    return os.environ.get("SSDK_GCONV_TRAIN", "1") != "0"
+
+
+def use_native_gconv(model):
+    """Switch every grouped 3x3 ``nn.Conv2d`` of ``model`` that ``supported`` accepts to the kernel-backed subclass (in place; no
+    new parameters, same ``state_dict``).  -> model; STATS["swapped"] counts the layers."""
+    for m in model.modules():
+        if type(m) is nn.Conv2d and supported(m):
+            m.__class__ = GroupedConv3x3
+            STATS["swapped"] += 1
+    return model

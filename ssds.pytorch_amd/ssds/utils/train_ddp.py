@@ -75,6 +75,12 @@ class Solver(object):
                 from ssds.modeling.layers.pointwise import fuse_conv_bn_statistics
 
                 fuse_conv_bn_statistics(self.model)  # the 1x1 kernels hand their BatchNorm the (local) batch statistics
+        from ssds.modeling.layers import groupedconv
+
+        if groupedconv.enabled():
+            # grouped 3x3 of the RegNetX / ResNeXt bottlenecks: forward, input gradient, weight gradient on csrc/ssdk_gconvtrain.hip
+            # (SSDK_GCONV_TRAIN=0: nn.Conv2d, i.e. MIOpen's grouped convolution behind autocast's weight cast)
+            groupedconv.use_native_gconv(self.model)
         from ssds.modeling.layers.pointwise import use_native_stem
 
         use_native_stem(self.model)  # the image-side 3x3 / stride-2 convolution: forward + weight gradient on csrc/ssdk_stemtrain.hip (A/B tools/run/r06_s42.sh: 17.0 vs 17.5 ms per step)

@@ -35,6 +35,9 @@ ap.add_argument("--sync-bn", type=int, default=0, choices=(0, 1),
                      "are measured")
 ap.add_argument("--optimizer", default="sgd", choices=("sgd", "adam", "amsgrad", "rmsprop"),
                 help="the config's optimizer (core/optimizer.configure_optimizer: the ssdk kernels on a HIP device)")
+ap.add_argument("--cfg", default="ssd_mobilenetv2_512.yml",
+                help="a config under experiments/cfgs (bifpn_regnetx016_896.yml, fpn_resnext50_640.yml: the grouped backbones; give a "
+                     "--batch that fits)")
 ap.add_argument("--size", type=int, default=0, help="square input size instead of the config's (300: planes that are not a multiple of 8)")
 ap.add_argument("--cpu", type=int, default=0,
                 help="(tests/test_ddp_cpu.py) 1: ONLY the launcher / rank / barrier / MAX-time / rank-0-print logic of this "
@@ -65,7 +68,7 @@ else:
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=dev)  # "nccl" is RCCL on ROCm
-cfg = config.cfg_from_file(os.path.join(ROOT, "experiments", "cfgs", "ssd_mobilenetv2_512.yml"))
+cfg = config.cfg_from_file(os.path.join(ROOT, "experiments", "cfgs", args.cfg))
 cfg.TRAIN.BATCH_SIZE = args.batch
 cfg.TRAIN.OPTIMIZER.OPTIMIZER = args.optimizer
 if args.size:
@@ -132,10 +135,11 @@ if world > 1:
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t)
 if rank == 0:
-    print(json.dumps({"metric": "images/sec (DDP training step) SSD-MobileNetV2@%d" % cfg.MODEL.IMAGE_SIZE[0], "value": round(world * args.batch * args.steps / el, 1),
+    _name = "SSD-MobileNetV2" if args.cfg == "ssd_mobilenetv2_512.yml" else "%s-%s" % (cfg.MODEL.SSDS, cfg.MODEL.NETS)
+    print(json.dumps({"metric": "images/sec (DDP training step) %s@%d" % (_name, cfg.MODEL.IMAGE_SIZE[0]), "value": round(world * args.batch * args.steps / el, 1),
                       "n_gpus": world, "ms_per_step": round(el / args.steps * 1e3, 2), "batch_per_gpu": args.batch,
                       "cls_loss": float(c), "loc_loss": float(l), "dtype": "bf16 autocast", "hipgraph": bool(args.graph), "sync_bn": bool(args.sync_bn),
-                      "optimizer": args.optimizer,
+                      "optimizer": args.optimizer, "cfg": args.cfg, "gconv_train": os.environ.get("SSDK_GCONV_TRAIN", "1") != "0",
                       "data": "synthetic" if not args.cpu else "stub (CPU / gloo run of the rank logic)"}))
 if world > 1:
     dist.destroy_process_group()
