@@ -529,6 +529,33 @@ size_t ssdk_gconv3x3_train_wgrad_workspace_bytes(int N, int C, int H, int W, int
 int ssdk_gconv3x3_train_wgrad(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int C, int H, int W,
                               int groups, int stride, int dtype, void* stream);
 
+/* The DENSE 3x3 convolution of the TRAINING step (towers, smoothing and heads of SSDFPN / SSDBiFPN, the ResNet bottleneck 3x3, the
+ * extras; csrc/ssdk_conv3train.hip): pad 1, stride 1 | 2, Cin a multiple of 16 in 16 .. 4096, Cout a multiple of 4 in 4 .. 4096,
+ * independent of each other.  16-bit tensors (SSDK_BF16 | SSDK_F16), NCHW contiguous in and out, 2-byte aligned; fp32 accumulation; no
+ * BatchNorm fold, no activation.  H, W are always the LAYER INPUT's size, Ho = (H - 1) / stride + 1.
+ * Dense 3x3 image of a weight tensor w[R][C][3][3] (R rows, C channels): the matrix m[16 * ceil(R / 16)][Kpad], Cp = 16 * ceil(C / 16),
+ * Kpad = 32 * ceil(9 * Cp / 32), m[r][tap * Cp + c] = w[r][c][tap / 3][tap % 3], zeros in rows >= R, channels >= C and columns
+ * >= 9 * Cp, stored as its fragment-major image (above): ssdk_weight_frag_bytes(R, Kpad) bytes.  With R == C it is the grouped image of
+ * one group.  The forward image is that of the weights (R = Cout, C = Cin), the input-gradient image that of
+ * W'[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx] (R = Cin, C = Cout).  Python twins: denseconv.pack_dense_frag / pack_dense_frag_dgrad.
+ *   ssdk_conv3x3_train_prepare   w32 [Cout, Cin, 3, 3] fp32 master weights -> w_fwd and / or w_dgrad (either may be NULL) in `dtype`,
+ *                                16-byte aligned, one launch.  Replaces autocast's cast of the parameter.
+ *   ssdk_conv3x3_train_forward   y [N, Cout, Ho, Wo] = conv(x [N, Cin, H, W], w_fwd) + bias (fp32 [Cout] or NULL, added in fp32 before
+ *                                the single rounding)
+ *   ssdk_conv3x3_train_dgrad     dx [N, Cin, H, W] = conv^T(dy [N, Cout, Ho, Wo], w_dgrad); stride 2 is a transposed convolution by
+ *                                input-pixel parity (9 taps per 2 x 2 input pixels), not a convolution over a zero-dilated dy
+ *   ssdk_conv3x3_train_wgrad     dw [Cout, Cin, 3, 3] fp32 = sum over pixels dy x; fp32 partial 64 x 64 tiles of pixel ranges through
+ *                                `workspace` (ssdk_conv3x3_train_wgrad_workspace_bytes, 16-byte aligned), added in index order:
+ *                                bit-reproducible, no atomics.  The workspace query returns 0 for a shape the kernels do not take. */
+int ssdk_conv3x3_train_prepare(const float* w32, void* w_fwd, void* w_dgrad, int Cin, int Cout, int dtype, void* stream);
+int ssdk_conv3x3_train_forward(const void* x, const void* w_fwd, const float* bias, void* y, int N, int Cin, int Cout, int H, int W,
+                               int stride, int dtype, void* stream);
+int ssdk_conv3x3_train_dgrad(const void* dy, const void* w_dgrad, void* dx, int N, int Cin, int Cout, int H, int W, int stride, int dtype,
+                             void* stream);
+size_t ssdk_conv3x3_train_wgrad_workspace_bytes(int N, int Cin, int Cout, int H, int W, int stride);
+int ssdk_conv3x3_train_wgrad(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int Cout,
+                             int H, int W, int stride, int dtype, void* stream);
+
 /* Weights of a 3x3 layer -- or of the loc | conf PAIR of an SSD level (reference ssd.py:100-103), w2 / b2 / n2 = NULL / NULL / 0
  * for a single layer -- from the fp32 master tensors [n, Cin, 3, 3] into the layouts ssdk_conv reads, in one launch (the head
  * convolutions of the TRAINING step run on the inference kernels: weights change every step): krsc = 16-bit [n1 + n2][3][3][Cin];

@@ -1,0 +1,186 @@
+"""Dense 3x3 convolutions of the training step on the NCHW tensors themselves (csrc/ssdk_conv3train.hip): the towers, smoothing
+and head convolutions of SSDFPN / SSDBiFPN, the 3x3 of the ResNet bottlenecks and the extras -- forward (+ bias), input gradient
+and weight gradient.
+
+PyTorch-ROCm sends a dense ``nn.Conv2d`` in bf16 to MIOpen's implicit GEMM, through autocast's cast of the weight and the
+library's own layout transposes.  ``DenseConv3x3`` is an ``nn.Conv2d`` (same parameters, ``state_dict`` keys and
+initialisation) whose 16-bit HIP-device forward / backward run on the ssdk kernels:
+
+    prepare          ssdk_conv3x3_train_prepare   fp32 master weight -> the 16-bit forward and input-gradient images
+    forward          ssdk_conv3x3_train_forward   y  = conv(x, W) + bias   (bias added in fp32, one rounding)
+    input gradient   ssdk_conv3x3_train_dgrad     dx = conv^T(dy, W)   (stride 2: by input-pixel parity, no zero-dilated dy)
+    weight gradient  ssdk_conv3x3_train_wgrad     dW fp32, pixel ranges added in index order: bit-reproducible
+
+pad 1, stride 1 | 2, groups 1, Cin a multiple of 16 in 16 .. 4096, Cout a multiple of 4 in 4 .. 4096.  CPU tensors, fp32
+tensors, non-contiguous tensors and every other layer shape take ``nn.Conv2d.forward``.
+
+The images are packed again by every call (one small launch): the native optimizers update parameters through raw pointers,
+so no tensor version counter says when a cached image is stale."""
+import os
+
+import torch
+import torch.nn as nn
+
+from ssds import _native as N
+
+MIN_CIN, MAX_CIN, MIN_COUT, MAX_COUT = 16, 4096, 4, 4096  # csrc/ssdk_conv3train.hip c3_shape_ok
+STATS = {"swapped": 0, "native_forward": 0, "native_dgrad": 0, "native_wgrad": 0}
+
+
+def shape_supported(cin, cout):
+    """The channel counts csrc/ssdk_conv3train.hip takes."""
+    return cin % 16 == 0 and MIN_CIN <= cin <= MAX_CIN and cout % 4 == 0 and MIN_COUT <= cout <= MAX_COUT
+
+
+def supported(m):
+    """``m`` is a dense 3x3 / pad 1 / stride 1 | 2 convolution of a supported shape."""
+    return (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.padding == (1, 1) and m.dilation == (1, 1)
+            and m.stride in ((1, 1), (2, 2)) and m.padding_mode == "zeros" and m.groups == 1
+            and shape_supported(m.in_channels, m.out_channels))
+
+
+def image_shape(rows, channels):
+    """-> (RB, KS, Cp) of the dense 3x3 image (include/ssdk.h) of a weight [rows, channels, 3, 3]."""
+    cp = (channels + 15) // 16 * 16
+    return (rows + 15) // 16, (9 * cp + 31) // 32, cp
+
+
+def pack_dense_frag(w):
+    """The dense 3x3 image of include/ssdk.h of OIHW weights ``w`` [R, C, 3, 3]: the matrix [16 ceil(R / 16)][Kpad] with
+    k = tap * Cp + c (Cp = C padded to 16, zeros in the padding), in fragment-major order [RB][KS][4][16][8].  Pure layout, on the
+    tensor's own device (CPU tensors too)."""
+    r, c, kh, kw = (int(v) for v in w.shape)
+    assert kh == 3 and kw == 3, tuple(w.shape)
+    rb, ks, cp = image_shape(r, c)
+    mat = w.new_zeros((rb * 16, ks * 32))
+    mat[:r, :9 * cp].view(r, 9, cp)[:, :, :c] = w.permute(0, 2, 3, 1).reshape(r, 9, c)
+    return mat.view(rb, 16, ks, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+
+
+def pack_dense_frag_dgrad(w):
+    """The image of the INPUT-GRADIENT weights W'[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]: at stride 1 dx = conv(dy, W'),
+    pad 1."""
+    return pack_dense_frag(w.flip(2, 3).transpose(0, 1))
+
+
+def unpack_dense_frag(img, rows, channels):
+    """The layout read backwards: image [RB][KS][4][16][8] -> OIHW weights [rows, channels, 3, 3]."""
+    rb, ks, cp = image_shape(rows, channels)
+    assert tuple(img.shape) == (rb, ks, 4, 16, 8), tuple(img.shape)
+    mat = img.permute(0, 3, 1, 2, 4).reshape(rb * 16, ks * 32)
+    return mat[:rows, :9 * cp].reshape(rows, 3, 3, cp)[:, :, :, :channels].permute(0, 3, 1, 2).contiguous()
+
+
+def prepare_images(weight, dtype, want_dgrad=True):
+    """fp32 (or 16-bit) weight [Cout, Cin, 3, 3] on a HIP device -> (forward image, input-gradient image | None) in ``dtype``, one
+    launch."""
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    dev = weight.device
+    w32 = weight.detach().float().contiguous()  # (a 16-bit weight survives the round trip exactly)
+    rb, ks, _ = image_shape(cout, cin)
+    fwd = torch.empty((rb, ks, 4, 16, 8), device=dev, dtype=dtype)
+    dg = None
+    if want_dgrad:
+        rb, ks, _ = image_shape(cin, cout)
+        dg = torch.empty((rb, ks, 4, 16, 8), device=dev, dtype=dtype)
+    with torch.cuda.device(dev):
+        N.check(N.lib.ssdk_conv3x3_train_prepare(w32.data_ptr(), fwd.data_ptr(), None if dg is None else dg.data_ptr(), cin, cout,
+                                                 N.dtype_code(fwd), N.stream_ptr(dev)), "conv3x3_train_prepare")
+    return fwd, dg
+
+
+class _DenseConv3x3(torch.autograd.Function):
+    """x [N, Cin, H, W] 16 bit, contiguous; weight [Cout, Cin, 3, 3] fp32 (the master parameter under autocast: the weight
+    gradient comes back in fp32) or in x's dtype; bias or None (added in fp32 by the forward kernel; its gradient is a torch sum)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride):
+        n, cin, h, wd = (int(v) for v in x.shape)
+        cout = int(weight.shape[0])
+        dev, dt = x.device, x.dtype
+        ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
+        code = N.dtype_code(x)
+        x = x.detach()
+        fwd, dg = prepare_images(weight, dt, want_dgrad=ctx.needs_input_grad[0])
+        b32 = None if bias is None else bias.detach().float().contiguous()
+        y = torch.empty((n, cout, ho, wo), device=dev, dtype=dt)
+        with torch.cuda.device(dev):
+            N.check(N.lib.ssdk_conv3x3_train_forward(x.data_ptr(), fwd.data_ptr(), None if b32 is None else b32.data_ptr(), y.data_ptr(),
+                                                     n, cin, cout, h, wd, stride, code, N.stream_ptr(dev)), "conv3x3_train_forward")
+        STATS["native_forward"] += 1
+        ctx.save_for_backward(x, dg)
+        ctx.meta = (weight.dtype, None if bias is None else bias.dtype, stride, cout)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, dg = ctx.saved_tensors
+        wdt, bdt, stride, cout = ctx.meta
+        n, cin, h, wd = (int(v) for v in x.shape)
+        dev, dt = x.device, x.dtype
+        gy = gy.contiguous()
+        if gy.dtype != dt:
+            gy = gy.to(dt)
+        code = N.dtype_code(x)
+        gx = gw = gb = None
+        with torch.cuda.device(dev):
+            sp = N.stream_ptr(dev)
+            if ctx.needs_input_grad[0]:
+                gx = torch.empty_like(x)
+                N.check(N.lib.ssdk_conv3x3_train_dgrad(gy.data_ptr(), dg.data_ptr(), gx.data_ptr(), n, cin, cout, h, wd, stride, code, sp),
+                        "conv3x3_train_dgrad")
+                STATS["native_dgrad"] += 1
+            if ctx.needs_input_grad[1]:
+                need = int(N.lib.ssdk_conv3x3_train_wgrad_workspace_bytes(n, cin, cout, h, wd, stride))
+                ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+                gw32 = torch.empty((cout, cin, 3, 3), device=dev, dtype=torch.float32)
+                N.check(N.lib.ssdk_conv3x3_train_wgrad(x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), (ws.data_ptr() + 15) & ~15, need,
+                                                       n, cin, cout, h, wd, stride, code, sp), "conv3x3_train_wgrad")
+                STATS["native_wgrad"] += 1
+                gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
+        if bdt is not None and ctx.needs_input_grad[2]:
+            gb = gy.sum((0, 2, 3), dtype=torch.float32).to(bdt)
+        return gx, gw, gb, None
+
+
+def dense_conv3x3(x, weight, bias=None, stride=1):
+    """The native path, called explicitly: x 16-bit contiguous NCHW on a HIP device; differentiable."""
+    return _DenseConv3x3.apply(x, weight, bias, stride)
+
+
+class DenseConv3x3(nn.Conv2d):
+    """``nn.Conv2d(Cin, Cout, 3, stride 1 | 2, pad 1)`` whose 16-bit HIP-device forward / backward run on
+    csrc/ssdk_conv3train.hip (same parameters, ``state_dict`` keys and initialisation); everything else is ``nn.Conv2d.forward``."""
+
+    def _native(self, x):
+        return x.is_cuda and x.dim() == 4 and x.is_contiguous() and int(x.shape[1]) == self.in_channels and supported(self)
+
+    def forward(self, x):
+        if not self._native(x):
+            return super(DenseConv3x3, self).forward(x)
+        w = self.weight
+        if torch.is_autocast_enabled():
+            x = x.to(torch.get_autocast_dtype("cuda"))
+        if x.dtype not in (torch.bfloat16, torch.float16) or (w.dtype != torch.float32 and w.dtype != x.dtype):
+            return super(DenseConv3x3, self).forward(x)
+        with torch.autocast("cuda", enabled=False):
+            return _DenseConv3x3.apply(x, w, self.bias, self.stride[0])
+
+
+DEFAULT = "1"  # provisional (docs/SWITCHES.md): to be re-decided from the per-layer probe and the step A/B
+
+
+def enabled():
+    """SSDK_DENSE3_TRAIN (docs/SWITCHES.md): 1 routes the dense 3x3 layers of the SSDFPN / SSDBiFPN training step to
+    csrc/ssdk_conv3train.hip, 0 leaves them on nn.Conv2d (extras: the im2col path)."""
+    return os.environ.get("SSDK_DENSE3_TRAIN", DEFAULT) != "0"
+
+
+def use_native_dense3x3(model):
+    """Switch every dense 3x3 ``nn.Conv2d`` of ``model`` that ``supported`` accepts to the kernel-backed subclass (in place; no
+    new parameters, same ``state_dict``).  -> model; STATS["swapped"] counts the layers."""
+    for m in model.modules():
+        if type(m) is nn.Conv2d and supported(m):
+            m.__class__ = DenseConv3x3
+            STATS["swapped"] += 1
+    return model

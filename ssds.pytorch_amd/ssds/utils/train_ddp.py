@@ -87,6 +87,15 @@ class Solver(object):
         from ssds.modeling.layers.headconv import use_head_pairs
 
         use_head_pairs(self.model)  # SSD heads: forward of each level's loc | conf pair on the inference kernels (SSDK_HEAD_PAIR=0: MIOpen)
+        from ssds.modeling.layers import denseconv
+        from ssds.modeling.ssds.bifpn import SSDBiFPN
+        from ssds.modeling.ssds.fpn import SSDFPN
+
+        if isinstance(self.model, (SSDFPN, SSDBiFPN)) and denseconv.enabled():
+            # dense 3x3 of the FPN / BiFPN detectors (towers, smoothing, heads, ResNet bottlenecks, extras): forward, input gradient,
+            # weight gradient on csrc/ssdk_conv3train.hip.  Before the im2col swap below, which then skips the extras of these
+            # models (no longer plain nn.Conv2d).  SSDK_DENSE3_TRAIN=0: nn.Conv2d / the im2col extras.  SSD models are not touched.
+            denseconv.use_native_dense3x3(self.model)
         conv3 = os.environ.get("SSDK_CONV3_NATIVE", "2")
         from ssds.modeling.layers import headconv
 
