@@ -556,6 +556,41 @@ size_t ssdk_conv3x3_train_wgrad_workspace_bytes(int N, int Cin, int Cout, int H,
 int ssdk_conv3x3_train_wgrad(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int Cout,
                              int H, int W, int stride, int dtype, void* stream);
 
+/* The memory-bound NECK operations of the TRAINING step of the FPN / BiFPN detectors (csrc/ssdk_necktrain.hip), forward and backward:
+ * the BiFPN weighted fusions, the FPN top-down upsample-add and the ResNet stem's max-pool.  16-bit tensors (SSDK_BF16 | SSDK_F16),
+ * NCHW contiguous, 2-byte aligned (rows of odd W take the scalar path); any C, H, W >= 1 below 2^31 elements; fp32 arithmetic, one
+ * rounding per output element; asynchronous on `stream`, every output fully written, no float atomics, no read-back:
+ * hipGraph-capturable.  Every argument check answers SSDK_E_BADARG before any device call.
+ *   ssdk_neck_fuse_fwd   y [N,C,H,W] = w0 a + w1 R_b(b) [+ w2 R_c(c)]   (c == NULL: two sources).  R = mode SSDK_FUSE_SAME | UP2 | POOL2
+ *                        with the geometry rules of ssdk_fuse: UP2 reads [N,C,H/2,W/2] (H, W even), POOL2 is max_pool2d(kernel 2) of
+ *                        [N,C,hb,wb] with hb / 2 == H and wb / 2 == W (floor mode drops an odd last row / column); hb, wb (hc, wc) are
+ *                        read under POOL2 only.  The weights are DEVICE fp32 values used as given: w_k = w[k * w_stride], so a column
+ *                        of a [K, L] tensor is (&t[0][col], L).  w == NULL: every weight is exactly 1 (the FPN upsample-add).  A NaN
+ *                        propagates through the max.
+ *   ssdk_neck_fuse_bwd   from gy [N,C,H,W], in one call (each output may be NULL when it is not needed):
+ *                          ga = w0 gy;   gb / gc by the source's mode: SAME w gy; UP2 w * (fp32 sum of the 2x2 block of gy in row-major
+ *                          order); POOL2 w gy at the window's arg-max and ZERO everywhere else, the dropped row / column included.  The
+ *                          arg-max is recomputed from the source: the first maximum in row-major window order, a NaN is a maximum.
+ *                          gw [nsrc][gw_cols] fp32, written whole: gw[k][gw_col] = sum gy R_k(x_k) over the tensor, zeros in the other
+ *                          columns.  Bit-reproducible: per-workgroup fp32 partials through `workspace`
+ *                          (ssdk_neck_fuse_bwd_workspace_bytes, 4-byte aligned, no initial contents required), added in index order by
+ *                          a second small launch.
+ *                        nsrc = 2 | 3.  With w == NULL ga and gw must be NULL (ga is gy itself).  Sources may be NULL where they are
+ *                        not read: all are read for gw, a POOL2 source for its own gradient.
+ *   ssdk_maxpool3x3s2_train_fwd   y [N,C,Ho,Wo] = max_pool2d(x [N,C,H,W], 3, stride 2, pad 1), Ho = (H - 1) / 2 + 1; pads with -inf,
+ *                                 propagates NaN.
+ *   ssdk_maxpool3x3s2_train_bwd   gx [N,C,H,W] from x and gy [N,C,Ho,Wo]: a gather, every gx element written exactly once; the same
+ *                                 first-maximum rule; a pixel that wins several windows gets the fp32 sum of their gy in window order,
+ *                                 rounded once.  No indices are kept. */
+int ssdk_neck_fuse_fwd(const void* a, const void* b, const void* c, const float* w, int w_stride, void* y, int N, int C, int H, int W,
+                       int mode_b, int hb, int wb, int mode_c, int hc, int wc, int dtype, void* stream);
+size_t ssdk_neck_fuse_bwd_workspace_bytes(int N, int C, int H, int W);
+int ssdk_neck_fuse_bwd(const void* gy, const void* a, const void* b, const void* c, int nsrc, const float* w, int w_stride, void* ga,
+                       void* gb, void* gc, float* gw, int gw_cols, int gw_col, void* workspace, size_t workspace_bytes, int N, int C,
+                       int H, int W, int mode_b, int hb, int wb, int mode_c, int hc, int wc, int dtype, void* stream);
+int ssdk_maxpool3x3s2_train_fwd(const void* x, void* y, int N, int C, int H, int W, int dtype, void* stream);
+int ssdk_maxpool3x3s2_train_bwd(const void* x, const void* gy, void* gx, int N, int C, int H, int W, int dtype, void* stream);
+
 /* Weights of a 3x3 layer -- or of the loc | conf PAIR of an SSD level (reference ssd.py:100-103), w2 / b2 / n2 = NULL / NULL / 0
  * for a single layer -- from the fp32 master tensors [n, Cin, 3, 3] into the layouts ssdk_conv reads, in one launch (the head
  * convolutions of the TRAINING step run on the inference kernels: weights change every step): krsc = 16-bit [n1 + n2][3][3][Cin];

@@ -186,6 +186,14 @@ def _load():
     lib.ssdk_conv3x3_train_wgrad.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, vp]
     for _n in ("ssdk_conv3x3_train_prepare", "ssdk_conv3x3_train_forward", "ssdk_conv3x3_train_dgrad", "ssdk_conv3x3_train_wgrad"):
         getattr(lib, _n).restype = i32
+    lib.ssdk_neck_fuse_fwd.argtypes = [vp, vp, vp, vp, i32, vp] + [i32] * 11 + [vp]
+    lib.ssdk_neck_fuse_bwd_workspace_bytes.argtypes = [i32] * 4
+    lib.ssdk_neck_fuse_bwd_workspace_bytes.restype = sz
+    lib.ssdk_neck_fuse_bwd.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, sz] + [i32] * 11 + [vp]
+    lib.ssdk_maxpool3x3s2_train_fwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.ssdk_maxpool3x3s2_train_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    for _n in ("ssdk_neck_fuse_fwd", "ssdk_neck_fuse_bwd", "ssdk_maxpool3x3s2_train_fwd", "ssdk_maxpool3x3s2_train_bwd"):
+        getattr(lib, _n).restype = i32
     lib.ssdk_pack_conv3x3.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.ssdk_pack_conv3x3.restype = i32
     lib.ssdk_pack_conv3x3_dgrad.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]
@@ -337,7 +345,8 @@ EXPORTS = ("ssdk_version", "ssdk_struct_size", "ssdk_abi_check", "ssdk_last_erro
            "ssdk_weight_frag_bytes", "ssdk_conv_workspace_bytes", "ssdk_conv", "ssdk_conv_sequence", "ssdk_mbconv", "ssdk_mbk_image_bytes", "ssdk_xpair", "ssdk_fuse", "ssdk_preprocess", "ssdk_augment_desc_bytes", "ssdk_augment_workspace_bytes", "ssdk_augment", "ssdk_dwconv_fwd_stats_workspace_bytes", "ssdk_dwconv_fwd_stats", "ssdk_dwconv_affine_supported", "ssdk_dwconv_fwd_affine", "ssdk_dwconv_bwd_weight_affine", "ssdk_bn_act_train_stats", "ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_stats_workspace_bytes", "ssdk_pw_forward_stats", "ssdk_bn_act_train_fwd_sums", "ssdk_pw_wgrad_workspace_bytes", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3", "ssdk_im2col3x3_folded", "ssdk_col2im3x3_folded", "ssdk_stem3x3s2_wgrad_workspace_bytes", "ssdk_stem3x3s2_fwd", "ssdk_stem3x3s2_wgrad", "ssdk_gconv3x3_train_prepare", "ssdk_gconv3x3_train_forward", "ssdk_gconv3x3_train_dgrad", "ssdk_gconv3x3_train_wgrad_workspace_bytes", "ssdk_gconv3x3_train_wgrad", "ssdk_conv3x3_train_prepare", "ssdk_conv3x3_train_forward", "ssdk_conv3x3_train_dgrad", "ssdk_conv3x3_train_wgrad_workspace_bytes", "ssdk_conv3x3_train_wgrad", "ssdk_pack_conv3x3", "ssdk_pack_conv3x3_dgrad", "ssdk_concat_nchw_to_nhwc", "ssdk_sgd_step", "ssdk_adam_step", "ssdk_rmsprop_step", "ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data",
            "ssdk_dwconv_bwd_weight_workspace_bytes", "ssdk_dwconv_bwd_weight", "ssdk_dwconv_plan", "ssdk_bn_workspace_bytes",
            "ssdk_bn_train_fwd", "ssdk_bn_train_bwd", "ssdk_bn_act_train_fwd", "ssdk_bn_act_train_bwd", "ssdk_bn_sync_local_stats",
-           "ssdk_bn_sync_fwd_finalize", "ssdk_bn_act_apply", "ssdk_bn_sync_bwd_local", "ssdk_bn_sync_bwd_apply", "ssdk_conv_stem7", "ssdk_maxpool3x3s2", "ssdk_run_ops", "ssdk_conv_bn_act", "ssdk_set_profiling", "ssdk_get_timings")
+           "ssdk_bn_sync_fwd_finalize", "ssdk_bn_act_apply", "ssdk_bn_sync_bwd_local", "ssdk_bn_sync_bwd_apply", "ssdk_conv_stem7", "ssdk_maxpool3x3s2", "ssdk_neck_fuse_fwd", "ssdk_neck_fuse_bwd_workspace_bytes", "ssdk_neck_fuse_bwd",
+           "ssdk_maxpool3x3s2_train_fwd", "ssdk_maxpool3x3s2_train_bwd", "ssdk_run_ops", "ssdk_conv_bn_act", "ssdk_set_profiling", "ssdk_get_timings")
 
 
 class Context(object):

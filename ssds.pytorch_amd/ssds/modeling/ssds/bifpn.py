@@ -14,7 +14,12 @@ from .ssdsbase import NeckPlanMixin, SSDSBase
 
 class BiFPNModule(nn.Module):
     """One BiFPN layer over ``levels`` maps of ``channels`` channels with fast-normalised fusion weights
-    (relu(w) / (sum relu(w) + 1e-6), reference bifpn.py:35-38)."""
+    (relu(w) / (sum relu(w) + 1e-6), reference bifpn.py:35-38).
+
+    ``native_neck`` (set by layers/neckfuse.py::use_native_neck): a fusion whose operands are 16-bit contiguous HIP tensors is one
+    launch of csrc/ssdk_necktrain.hip, forward and backward, with the fp32 normalised weights read from device memory."""
+
+    native_neck = False
 
     def __init__(self, channels, levels, init=0.5, block=ConvBNReLU):
         super(BiFPNModule, self).__init__()
@@ -38,16 +43,27 @@ class BiFPNModule(nn.Module):
         w1 = w1 / (torch.sum(w1, dim=0) + 1e-6)
         w2 = F.relu(self.w2)
         w2 = w2 / (torch.sum(w2, dim=0) + 1e-6)
+        fuse = None
+        if self.native_neck:
+            from ssds.modeling.layers import neckfuse as NF
+
+            fuse, w1n, w2n = NF.try_fuse, w1, w2  # None from try_fuse: the operands are not the kernels', the eager lines below run
         w1 = w1.to(xx[0].dtype)
         w2 = w2.to(xx[0].dtype)
         skips = [None] + [x for x in xx[1:-1]] + [None]
         for i in range(n - 1, 0, -1):  # top-down (reference bifpn.py:41-46)
-            fused = w1[0, i - 1] * xx[i - 1] + w1[1, i - 1] * F.interpolate(xx[i], scale_factor=2, mode="nearest")
+            fused = fuse(xx[i - 1], xx[i], None, w1n, i - 1, NF.UP2) if fuse else None
+            if fused is None:
+                fused = w1[0, i - 1] * xx[i - 1] + w1[1, i - 1] * F.interpolate(xx[i], scale_factor=2, mode="nearest")
             xx[i - 1] = getattr(self, "top-down-{}".format(i - 1))(fused)
         for i in range(0, n - 2, 1):  # bottom-up with skip (reference bifpn.py:49-55)
-            fused = w2[0, i] * xx[i + 1] + w2[1, i] * F.max_pool2d(xx[i], kernel_size=2) + w2[2, i] * skips[i + 1]
+            fused = fuse(xx[i + 1], xx[i], skips[i + 1], w2n, i, NF.POOL2, NF.SAME) if fuse else None
+            if fused is None:
+                fused = w2[0, i] * xx[i + 1] + w2[1, i] * F.max_pool2d(xx[i], kernel_size=2) + w2[2, i] * skips[i + 1]
             xx[i + 1] = getattr(self, "bottom-up-{}".format(i + 1))(fused)
-        fused = w1[0, n - 1] * xx[n - 1] + w1[1, n - 1] * F.max_pool2d(xx[n - 2], kernel_size=2)
+        fused = fuse(xx[n - 1], xx[n - 2], None, w1n, n - 1, NF.POOL2) if fuse else None
+        if fused is None:
+            fused = w1[0, n - 1] * xx[n - 1] + w1[1, n - 1] * F.max_pool2d(xx[n - 2], kernel_size=2)
         xx[n - 1] = getattr(self, "bottom-up-{}".format(n - 1))(fused)  # reference bifpn.py:57-62
         return xx
 

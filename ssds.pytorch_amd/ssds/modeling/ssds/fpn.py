@@ -60,7 +60,12 @@ def _final_conv(owner, conv, x, act):
 
 
 class SSDFPN(NeckPlanMixin, SSDSBase):
-    """RetinaNet (https://arxiv.org/abs/1708.02002) with ConvBNReLU extras/towers like the reference."""
+    """RetinaNet (https://arxiv.org/abs/1708.02002) with ConvBNReLU extras/towers like the reference.
+
+    ``native_neck`` (set by layers/neckfuse.py::use_native_neck): a top-down step whose operands are 16-bit contiguous HIP tensors
+    is one launch of csrc/ssdk_necktrain.hip, forward and backward."""
+
+    native_neck = False
 
     def __init__(self, backbone, extras, head, num_classes):
         super(SSDFPN, self).__init__(backbone, num_classes)
@@ -101,6 +106,13 @@ class SSDFPN(NeckPlanMixin, SSDSBase):
         xx = None
         for i in range(n - 1, -1, -1):  # top-down pathway (reference fpn.py:80-87)
             lateral = self.transforms[i](features[i])
+            if self.native_neck and i < n - 1:
+                from ssds.modeling.layers import neckfuse as NF
+
+                fused = NF.try_fuse(lateral, xx, mode_b=NF.UP2)  # None: not the kernels' operands, the eager line below runs
+                if fused is not None:
+                    features[i] = xx = fused
+                    continue
             xx = lateral if i == n - 1 else F.interpolate(xx, scale_factor=2, mode="nearest") + lateral
             features[i] = xx
         for i, v in enumerate(self.extras):  # reference fpn.py:89-97

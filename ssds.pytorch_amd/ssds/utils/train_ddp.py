@@ -96,6 +96,12 @@ class Solver(object):
             # weight gradient on csrc/ssdk_conv3train.hip.  Before the im2col swap below, which then skips the extras of these
             # models (no longer plain nn.Conv2d).  SSDK_DENSE3_TRAIN=0: nn.Conv2d / the im2col extras.  SSD models are not touched.
             denseconv.use_native_dense3x3(self.model)
+        from ssds.modeling.layers import neckfuse
+
+        if isinstance(self.model, (SSDFPN, SSDBiFPN)) and neckfuse.enabled():
+            # the BiFPN weighted fusions, the FPN top-down upsample-adds and the ResNet stem's max-pool: forward and backward on
+            # csrc/ssdk_necktrain.hip.  SSDK_NECK_TRAIN=0: the eager expressions / nn.MaxPool2d.  SSD models are not touched.
+            neckfuse.use_native_neck(self.model)
         conv3 = os.environ.get("SSDK_CONV3_NATIVE", "2")
         from ssds.modeling.layers import headconv
 
