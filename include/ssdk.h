@@ -644,8 +644,11 @@ int ssdk_rmsprop_step(int n, void* const* params, const void* const* grads, void
  *   fwd:        x [N,C,H,W], w [C,1,3,3] -> y [N,C,Ho,Wo]
  *   bwd_data:   dy [N,C,Ho,Wo], w -> dx [N,C,H,W]           (H, W are the INPUT dims in all three calls)
  *   bwd_weight: x, dy -> dw fp32 [C,1,3,3]; two-stage fixed-order reduction (bit-reproducible) through `workspace`
- * Any plane size; pointers need only the alignment of their element type (rows are read and written as unaligned
- * 16-byte runs). */
+ * Any plane size; x, w, dy, y and dx need only the alignment of their element type (2 bytes for the 16-bit types), dw and the
+ * weight-gradient workspace that of a float: the whole-row kernels read and write rows as unaligned 16-byte runs, the tiled kernels
+ * take their 16-byte paths only where base pointer and row are aligned and go element by element otherwise.  No byte outside the
+ * tensors is read into a result or written (tests/test_gpu_dwtrain.py: 2-, 6- and 8-byte aligned views between NaN guards, both
+ * kernel families, bit-equal to aligned copies). */
 int ssdk_dwconv_fwd(const void* x, const void* w, void* y, int N, int C, int H, int W, int stride, int dtype, void* stream);
 /* (version 240) forward + sums [C][2] = per channel (sum y, sum y^2) over N * Ho * Wo of its outputs (fp32 accumulators, before the
  * store's rounding): the batch statistics of the BatchNorm behind the convolution (ssdk_bn_act_train_fwd_sums), without a pass over

@@ -17,6 +17,29 @@ def _launch(fn, *args):
     N.check(fn(*args), fn.__name__)
 
 
+# The longest chain of dependent fp32 additions a product of the weight gradient passes through, in either kernel family (the bar
+# of tests/test_gpu_dwtrain.py: |dW - truth| <= DW_SUM_DEPTH 2^-24 sum |dy x|).
+#   whole rows (csrc/ssdk_dwplane.hip): dwp_wgrad_kernel -- a thread owns <= kDwpMaxPass = 4 units and adds the 4 pixel pairs of a
+#     unit into acc2[tap] by fused multiply-adds (16), then the two halves of the pair (1), the xor tree of the wave (6) and the
+#     four waves in order (3); dwp_wgrad_reduce_kernel -- lane l adds the groups l, l + 64, ... (P = ceil(groups / 64)), then the
+#     xor tree (6):                                                        16 + 1 + 6 + 3 + P + 6 = 32 + P
+#   tiles (csrc/ssdk_dwtrain.hip): dw_wgrad_kernel -- a thread adds its 8 pixels into acc[tap] (8), the xor tree (6), the four waves
+#     (3); dw_wgrad_reduce_kernel -- lane l adds the (image, tile) partials l, l + 64, ... (P = ceil(N tiles / 64)), then the xor
+#     tree (6):                                                            8 + 6 + 3 + P + 6 = 23 + P
+#   + 1 for the product itself: the tiled kernels multiply, round and then add (the library is built with -ffp-contract=off), which
+#     counts for fp32 operands (the product of two 16-bit values is exact in fp32).
+# P grows with the batch, so the constant is NOT a property of the kernels for any N: P = 4 is a bound for up to 256 partial sums
+# per channel, which covers every shape of the tests (at most 6 groups, 176 tiles; tests/test_dwjudge_cpu.py checks this against the
+# library's plan) and the 150 x 150 layers of the workload at batch 64 (192 groups).  A batch-128 150 x 150 layer has 384 groups
+# (P = 6).
+DW_SUM_DEPTH = 16 + 1 + 6 + 3 + 4 + 6 + 1
+# ... and a term of the statistics sums (ssdk_dwconv_fwd_stats / _fwd_affine: sum y, sum y^2 of the fp32 accumulators): dwp_fwd_kernel
+# -- a thread adds the 8 pixels of its <= 4 units (32), the xor tree (6), the four waves onto zero (4); pw_wgrad_reduce_kernel
+# (csrc/ssdk_pwtrain.hip), one pass per factor 64 of the <= 4096 groups the workspace function admits, so at most two -- 16 rows in a
+# chain (15) and the four quarters (3) each; + 1 for the square, which is rounded before it is added.
+DW_STATS_DEPTH = 32 + 6 + 4 + 2 * (15 + 3) + 1
+
+
 class _DwConv3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, stride, want_sums=False, coef=None, act=0):

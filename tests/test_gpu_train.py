@@ -301,7 +301,8 @@ def test_a_skipped_first_step_leaves_zero_momentum(opt_kind):
                                             (6, 1, 38, 38, 7), (6, 2, 38, 38, 7), (4, 1, 19, 19, 27), (4, 2, 19, 19, 27),
                                             (2, 1, 10, 10, 70), (3, 1, 1, 1, 2), (2, 2, 3, 3000, 1)])
 def test_depthwise_autograd_kernels_match_torch(c, stride, h, w, n, dtype_name, tol):
-    """forward / input gradient / weight gradient of the training depthwise kernels vs torch fp32 autograd."""
+    """forward / input gradient / weight gradient of the training depthwise kernels vs torch fp32 autograd.
+    (A max-norm against the library; the per-element judgement against fp64, per kernel family, is tests/test_gpu_dwtrain.py.)"""
     import torch
     import torch.nn.functional as F
     from ssds.modeling.layers.dwconv import DepthwiseConv2d
