@@ -505,6 +505,21 @@ int ssdk_stem3x3s2_fwd(const void* x, const float* w, void* y, int N, int Cin, i
 int ssdk_stem3x3s2_wgrad(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int H, int W,
                          int Cout, int dtype, void* stream);
 
+/* The 7x7 / stride 2 / pad 3 image-side convolution of the ResNet / ResNeXt backbones inside the training step (Cin <= 3 image
+ * channels, Cout <= 64, bias-free: nets/resnet.py conv1) on its own kernels (csrc/ssdk_stem7train.hip) -- an image has no input gradient:
+ *   ssdk_stem7x7s2_fwd     x [N, Cin, H, W] 16 bit, w [Cout, Cin, 7, 7] fp32 master weights (rounded to the tensor dtype inside,
+ *                          like autocast's cast) -> y [N, Cout, Ho, Wo] 16 bit, fp32 accumulation on the matrix cores, one rounding
+ *                          on store; Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1
+ *   ssdk_stem7x7s2_wgrad   x, dy [N, Cout, Ho, Wo] 16 bit -> dw [Cout, Cin, 7, 7] fp32 (matrix cores over pixels, wave partials added
+ *                          in wave order, workgroup partials in index order: bit-reproducible, no atomics)
+ * Tensors are NCHW contiguous, 2-byte aligned (aligned tensors with rows of whole 16-byte groups take the vector-load forms).
+ * workspace of the weight gradient: ssdk_stem7x7s2_wgrad_workspace_bytes(N, H, W, Cout) bytes (0 for invalid arguments), 16-byte
+ * aligned. */
+size_t ssdk_stem7x7s2_wgrad_workspace_bytes(int N, int H, int W, int Cout);
+int ssdk_stem7x7s2_fwd(const void* x, const float* w, void* y, int N, int Cin, int H, int W, int Cout, int dtype, void* stream);
+int ssdk_stem7x7s2_wgrad(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int H, int W,
+                         int Cout, int dtype, void* stream);
+
 /* The grouped 3x3 convolution of the TRAINING step (RegNetX / ResNeXt bottlenecks: nets/regnet.py, nets/resnet.py; csrc/ssdk_gconvtrain.hip):
  * pad 1, stride 1 | 2, C == groups * gw input and output channels, gw = 4 (an even number of groups) or a multiple of 8 up to 256
  * (16 included).  16-bit tensors (SSDK_BF16 | SSDK_F16), NCHW contiguous in and out, 2-byte aligned; fp32 accumulation; no BatchNorm

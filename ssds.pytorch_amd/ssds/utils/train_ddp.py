@@ -84,6 +84,12 @@ class Solver(object):
         from ssds.modeling.layers.pointwise import use_native_stem
 
         use_native_stem(self.model)  # the image-side 3x3 / stride-2 convolution: forward + weight gradient on csrc/ssdk_stemtrain.hip (A/B tools/run/r06_s42.sh: 17.0 vs 17.5 ms per step)
+        from ssds.modeling.layers import stemconv
+
+        if stemconv.enabled():
+            # the 7x7 / stride-2 stem of the ResNet / ResNeXt backbones (any detector on them): forward + weight gradient on
+            # csrc/ssdk_stem7train.hip.  SSDK_STEM7_TRAIN=0: nn.Conv2d, i.e. the library convolution behind autocast's weight cast
+            stemconv.use_native_stem7(self.model)
         from ssds.modeling.layers.headconv import use_head_pairs
 
         use_head_pairs(self.model)  # SSD heads: forward of each level's loc | conf pair on the inference kernels (SSDK_HEAD_PAIR=0: MIOpen)
