@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 245 /* 0.2.4.5: the BatchNorm workspace begins with ticket words that must be zero when it is first used (ssdk_bn_workspace_bytes); 0.2.4.4: ssdk_im2col3x3_folded / ssdk_col2im3x3_folded; 0.2.4.3: ssdk_stem3x3s2_fwd / _wgrad (the first convolution of the training step); 0.2.4.2: ssdk_concat_nchw_to_nhwc; 0.2.4.1: ssdk_pack_conv3x3[_dgrad]; 0.2.4: ssdk_abi_check, ssdk_pw_* (1x1 convolutions of the training step: forward / input gradient / weight gradient on NCHW tensors); 0.2.3: ssdk_struct_size; 0.2.2: ssdk_mbconv_desc.image_nw / w_image / w_image_bytes (ssdk_mbk.hip), larger ssdk_match_multibox_loss workspace; 0.2.1: ssdk_match_multibox_loss, ssdk_op.lane == 2; fields appended to descriptors since 200 (zero = old behaviour) */
+#define SSDK_VERSION 245 /* (still 245 with ssdk_mbse / SSDK_OP_MBSE / ssdk_op.mbse: the number is pinned by the callers in the field, and a stale caller is rejected all the same because ssdk_abi_check compares sizeof(ssdk_op), which grew with the appended member) 0.2.4.5: the BatchNorm workspace begins with ticket words that must be zero when it is first used (ssdk_bn_workspace_bytes); 0.2.4.4: ssdk_im2col3x3_folded / ssdk_col2im3x3_folded; 0.2.4.3: ssdk_stem3x3s2_fwd / _wgrad (the first convolution of the training step); 0.2.4.2: ssdk_concat_nchw_to_nhwc; 0.2.4.1: ssdk_pack_conv3x3[_dgrad]; 0.2.4: ssdk_abi_check, ssdk_pw_* (1x1 convolutions of the training step: forward / input gradient / weight gradient on NCHW tensors); 0.2.3: ssdk_struct_size; 0.2.2: ssdk_mbconv_desc.image_nw / w_image / w_image_bytes (ssdk_mbk.hip), larger ssdk_match_multibox_loss workspace; 0.2.1: ssdk_match_multibox_loss, ssdk_op.lane == 2; fields appended to descriptors since 200 (zero = old behaviour) */
 
 #define SSDK_MAX_LEVELS 8    /* feature-map levels per decode_nms call            */
 #define SSDK_MAX_ANCHORS 16  /* anchors per location (A)                          */
@@ -824,7 +824,50 @@ int ssdk_xpair(const ssdk_xpair_desc* desc, void* stream);
  * towers + heads of the small pyramid levels next to the big levels' launches) -- the kernel choice for an op that may
  * underfill the chip (no split-K), made from the tag alone, so the outputs do not depend on whether the side lane is on.
  * Buffers read or written by side ops must not be reused by later ops of the list. */
-enum { SSDK_OP_CONV = 0, SSDK_OP_MBCONV = 1, SSDK_OP_FUSE = 2, SSDK_OP_STEM7 = 3, SSDK_OP_POOL = 4, SSDK_OP_XPAIR = 5 };
+
+/* The tail of an EfficientNet MBConv block (nets/efficientnet.py MBConvBlock; csrc/ssdk_mbse.hip) -- everything behind the
+ * expand 1x1, which stays an ordinary ssdk_conv with act = SILU:
+ *   x [N][H][W][C]  --depthwise k x k, stride s, pad k/2, folded BN, SiLU-->  t [N][Ho][Wo][C]      Ho = (H - 1) / s + 1
+ *   mean[n][c] = mean of t over the image's plane;  gate [N][C] fp32 = sigmoid(W2 silu(W1 mean + b1) + b2)
+ *   y [N][Ho][Wo][Cout] = (sum_c round(t * gate[n][c]) * w_proj[co][c]) * scale_proj[co] + bias_proj[co] (+ residual)
+ * NHWC, dtype SSDK_BF16 | SSDK_F16 (x, t, y, residual, w_dw, w_proj); everything else fp32.  The product t * gate is rounded
+ * to the tensor dtype on its way into the matrix product (what a 16-bit `x * se(x)` stores); y is rounded once, after the
+ * residual add.  Three launches, no allocation, no synchronisation, no atomics (bit-reproducible):
+ *   stages  bit mask, 0 = all: 1 = depthwise + pool partials (writes t, pool_partial), 2 = gate (reads pool_partial, writes
+ *           gate), 4 = gated projection (reads t, gate, residual; writes y).  Only the buffers of the requested stages are read
+ *           or checked, so a caller may run one stage on inputs of its own (tests: a hand-made gate).
+ *   pool_partial  fp32 [N][T][C], T = ssdk_mbse_pool_tiles(H, W, k, stride): per 16 x 16 tile of output pixels the sum of t AS
+ *           STORED (after rounding), written once each; stage 2 adds the tiles in a fixed order.
+ *   w_dw [k][k][C] tensor dtype, scale_dw / bias_dw fp32 [C] (folded BN);  w_se1 [R][C], b_se1 [R], w_se2 [C][R], b_se2 [C] fp32;
+ *   w_proj [Cout][C] tensor dtype, scale_proj / bias_proj fp32 [Cout] (folded BN);  residual optional, [N][Ho][Wo][Cout].
+ * Accepted: C, Cout multiples of 8 (C <= 4096), k 3 | 5, stride 1 | 2, 1 <= R <= 1024, any H, W >= 1 (maps smaller than the
+ * window included), N <= 65535; tensors, weights, gate, pool_partial and the folded BN vectors 16-byte aligned.  Anything else
+ * is SSDK_E_BADARG with a message before any launch.  Not part of ssdk_struct_size(): ssdk_mbse_desc_bytes() reports its size. */
+typedef struct ssdk_mbse_desc {
+  const void* x;
+  void* t;
+  float* pool_partial;
+  float* gate;
+  void* y;
+  const void* residual;
+  const void* w_dw;
+  const float* scale_dw;
+  const float* bias_dw;
+  const float* w_se1;
+  const float* b_se1;
+  const float* w_se2;
+  const float* b_se2;
+  const void* w_proj;
+  const float* scale_proj;
+  const float* bias_proj;
+  int32_t N, H, W, C, R, Cout, k, stride, dtype, stages;
+} ssdk_mbse_desc;
+int ssdk_mbse(const ssdk_mbse_desc* desc, void* stream);
+int ssdk_mbse_pool_tiles(int H, int W, int k, int stride); /* 0 for arguments ssdk_mbse does not take */
+size_t ssdk_mbse_desc_bytes(void);
+
+enum { SSDK_OP_CONV = 0, SSDK_OP_MBCONV = 1, SSDK_OP_FUSE = 2, SSDK_OP_STEM7 = 3, SSDK_OP_POOL = 4, SSDK_OP_XPAIR = 5,
+       SSDK_OP_MBSE = 6 /* lane 0 only */ };
 typedef struct ssdk_op {
   int32_t kind, lane;
   ssdk_conv_desc conv;
@@ -833,6 +876,7 @@ typedef struct ssdk_op {
   ssdk_stem_desc stem;
   ssdk_pool_desc pool;
   ssdk_xpair_desc xpair;
+  ssdk_mbse_desc mbse; /* appended with SSDK_OP_MBSE: sizeof(ssdk_op) grew, which ssdk_abi_check sees */
 } ssdk_op;
 int ssdk_run_ops(const ssdk_op* ops, int n, void* workspace, size_t workspace_bytes, void* stream);
 int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* workspace, size_t workspace_bytes, void* stream);

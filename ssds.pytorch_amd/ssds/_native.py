@@ -93,12 +93,21 @@ class AugmentDesc(ctypes.Structure):
         ("color", ctypes.c_float * 12), ("fill", ctypes.c_float * 3)]
 
 
+class MbSeDesc(ctypes.Structure):
+    """ssdk_mbse_desc: the tail of an EfficientNet MBConv block (depthwise + SE gate + gated projection)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "x", "t", "pool_partial", "gate", "y", "residual", "w_dw", "scale_dw", "bias_dw", "w_se1", "b_se1", "w_se2", "b_se2",
+        "w_proj", "scale_proj", "bias_proj")] + [(n, ctypes.c_int32) for n in (
+            "N", "H", "W", "C", "R", "Cout", "k", "stride", "dtype", "stages")]
+
+
 class Op(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("lane", ctypes.c_int32), ("conv", ConvDesc), ("mb", MbConvDesc),
-                ("fuse", FuseDesc), ("stem", StemDesc), ("pool", PoolDesc), ("xpair", XpairDesc)]
+                ("fuse", FuseDesc), ("stem", StemDesc), ("pool", PoolDesc), ("xpair", XpairDesc), ("mbse", MbSeDesc)]
 
 
-OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR = 0, 1, 2, 3, 4, 5
+OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE = 0, 1, 2, 3, 4, 5, 6
+MBSE_DW, MBSE_GATE, MBSE_PROJ = 1, 2, 4  # ssdk_mbse_desc.stages bits (0 = all three)
 FUSE_SAME, FUSE_UP2, FUSE_POOL2 = 0, 1, 2
 NCHW, NHWC = 0, 1
 
@@ -320,6 +329,17 @@ def _load():
         raise ImportError("libssdk.so at {} has sizeof(ssdk_augment_desc) = {} but ssds/_native.py mirrors it with {} bytes: "
                           "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, int(lib.ssdk_augment_desc_bytes()),
                                                                                c.sizeof(AugmentDesc)))
+    # ssdk_mbse_desc is not behind ssdk_struct_size either (its eight indices are pinned): same arrangement
+    lib.ssdk_mbse_desc_bytes.restype = sz
+    lib.ssdk_mbse_desc_bytes.argtypes = []
+    if int(lib.ssdk_mbse_desc_bytes()) != c.sizeof(MbSeDesc):
+        raise ImportError("libssdk.so at {} has sizeof(ssdk_mbse_desc) = {} but ssds/_native.py mirrors it with {} bytes: "
+                          "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, int(lib.ssdk_mbse_desc_bytes()),
+                                                                               c.sizeof(MbSeDesc)))
+    lib.ssdk_mbse.argtypes = [c.POINTER(MbSeDesc), vp]
+    lib.ssdk_mbse.restype = i32
+    lib.ssdk_mbse_pool_tiles.argtypes = [i32] * 4
+    lib.ssdk_mbse_pool_tiles.restype = i32
     lib.ssdk_augment_workspace_bytes.restype = sz
     lib.ssdk_augment_workspace_bytes.argtypes = [i32]
     lib.ssdk_augment.argtypes = [vp, sz, c.POINTER(AugmentDesc), i32, i32, i32, c.POINTER(f32), c.POINTER(f32), vp, i32, vp, sz, vp]
@@ -347,7 +367,7 @@ EXPORTS = ("ssdk_version", "ssdk_struct_size", "ssdk_abi_check", "ssdk_last_erro
            "ssdk_ctx_create", "ssdk_ctx_destroy", "ssdk_ctx_set_tail_stream", "ssdk_ctx_set_side_lane", "ssdk_ctx_set_profiling",
            "ssdk_ctx_get_timings", "ssdk_ctx_set_op_profiling", "ssdk_ctx_get_op_timings", "ssdk_ctx_get_tail_stamps",
            "ssdk_run_ops_ctx", "ssdk_decode_nms_ctx",
-           "ssdk_weight_frag_bytes", "ssdk_conv_workspace_bytes", "ssdk_conv", "ssdk_conv_sequence", "ssdk_mbconv", "ssdk_mbk_image_bytes", "ssdk_xpair", "ssdk_fuse", "ssdk_preprocess", "ssdk_augment_desc_bytes", "ssdk_augment_workspace_bytes", "ssdk_augment", "ssdk_dwconv_fwd_stats_workspace_bytes", "ssdk_dwconv_fwd_stats", "ssdk_dwconv_affine_supported", "ssdk_dwconv_fwd_affine", "ssdk_dwconv_bwd_weight_affine", "ssdk_bn_act_train_stats", "ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_stats_workspace_bytes", "ssdk_pw_forward_stats", "ssdk_bn_act_train_fwd_sums", "ssdk_pw_wgrad_workspace_bytes", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3", "ssdk_im2col3x3_folded", "ssdk_col2im3x3_folded", "ssdk_stem3x3s2_wgrad_workspace_bytes", "ssdk_stem3x3s2_fwd", "ssdk_stem3x3s2_wgrad", "ssdk_stem7x7s2_wgrad_workspace_bytes", "ssdk_stem7x7s2_fwd", "ssdk_stem7x7s2_wgrad", "ssdk_gconv3x3_train_prepare", "ssdk_gconv3x3_train_forward", "ssdk_gconv3x3_train_dgrad", "ssdk_gconv3x3_train_wgrad_workspace_bytes", "ssdk_gconv3x3_train_wgrad", "ssdk_conv3x3_train_prepare", "ssdk_conv3x3_train_forward", "ssdk_conv3x3_train_dgrad", "ssdk_conv3x3_train_wgrad_workspace_bytes", "ssdk_conv3x3_train_wgrad", "ssdk_pack_conv3x3", "ssdk_pack_conv3x3_dgrad", "ssdk_concat_nchw_to_nhwc", "ssdk_sgd_step", "ssdk_adam_step", "ssdk_rmsprop_step", "ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data",
+           "ssdk_weight_frag_bytes", "ssdk_conv_workspace_bytes", "ssdk_conv", "ssdk_conv_sequence", "ssdk_mbconv", "ssdk_mbk_image_bytes", "ssdk_mbse", "ssdk_mbse_pool_tiles", "ssdk_mbse_desc_bytes", "ssdk_xpair", "ssdk_fuse", "ssdk_preprocess", "ssdk_augment_desc_bytes", "ssdk_augment_workspace_bytes", "ssdk_augment", "ssdk_dwconv_fwd_stats_workspace_bytes", "ssdk_dwconv_fwd_stats", "ssdk_dwconv_affine_supported", "ssdk_dwconv_fwd_affine", "ssdk_dwconv_bwd_weight_affine", "ssdk_bn_act_train_stats", "ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_stats_workspace_bytes", "ssdk_pw_forward_stats", "ssdk_bn_act_train_fwd_sums", "ssdk_pw_wgrad_workspace_bytes", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3", "ssdk_im2col3x3_folded", "ssdk_col2im3x3_folded", "ssdk_stem3x3s2_wgrad_workspace_bytes", "ssdk_stem3x3s2_fwd", "ssdk_stem3x3s2_wgrad", "ssdk_stem7x7s2_wgrad_workspace_bytes", "ssdk_stem7x7s2_fwd", "ssdk_stem7x7s2_wgrad", "ssdk_gconv3x3_train_prepare", "ssdk_gconv3x3_train_forward", "ssdk_gconv3x3_train_dgrad", "ssdk_gconv3x3_train_wgrad_workspace_bytes", "ssdk_gconv3x3_train_wgrad", "ssdk_conv3x3_train_prepare", "ssdk_conv3x3_train_forward", "ssdk_conv3x3_train_dgrad", "ssdk_conv3x3_train_wgrad_workspace_bytes", "ssdk_conv3x3_train_wgrad", "ssdk_pack_conv3x3", "ssdk_pack_conv3x3_dgrad", "ssdk_concat_nchw_to_nhwc", "ssdk_sgd_step", "ssdk_adam_step", "ssdk_rmsprop_step", "ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data",
            "ssdk_dwconv_bwd_weight_workspace_bytes", "ssdk_dwconv_bwd_weight", "ssdk_dwconv_plan", "ssdk_bn_workspace_bytes",
            "ssdk_bn_train_fwd", "ssdk_bn_train_bwd", "ssdk_bn_act_train_fwd", "ssdk_bn_act_train_bwd", "ssdk_bn_sync_local_stats",
            "ssdk_bn_sync_fwd_finalize", "ssdk_bn_act_apply", "ssdk_bn_sync_bwd_local", "ssdk_bn_sync_bwd_apply", "ssdk_conv_stem7", "ssdk_maxpool3x3s2", "ssdk_neck_fuse_fwd", "ssdk_neck_fuse_bwd_workspace_bytes", "ssdk_neck_fuse_bwd",

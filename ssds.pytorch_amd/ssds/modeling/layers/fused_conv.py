@@ -410,6 +410,143 @@ class MbPack(object):
         return bool(bound.max() < 3.0e4)
 
 
+# ---- EfficientNet MBConv tail (csrc/ssdk_mbse.hip): depthwise k x k + SiLU, squeeze-excite gate, gated projection ----------
+# SSDK_MBSE=0 (read when a plan is recorded): planner.record_efficientnet raises PlanUnsupported, so an EfficientNet backbone
+# runs module by module on PyTorch-ROCm (A/B measurements only; docs/SWITCHES.md).
+def mbse_enabled():
+    return os.environ.get("SSDK_MBSE", "1") != "0"
+
+
+MBSE_TILE = 16  # output pixels per tile side of mbse_dw_kernel (ssdk_mbse_pool_tiles)
+
+
+def mbse_pool_tiles(h, w, k, stride):
+    """T of pool_partial [N][T][C] -- the Python mirror of ssdk_mbse_pool_tiles (the CPU-side plan walk has no library call
+    to make for it; tests compare the two)."""
+    ho, wo = _out_hw(h, w, k, stride)
+    return ((ho + MBSE_TILE - 1) // MBSE_TILE) * ((wo + MBSE_TILE - 1) // MBSE_TILE)
+
+
+# Summation depths of the three mbse kernels = the longest chain of fp32 additions an input term passes through (what the
+# error bars of tests/mbseaudit.py are derived from, as dwconv.DW_SUM_DEPTH is for the depthwise training kernels):
+#   pool:  a lane of mbse_dw_kernel adds the pixels of its slot in index order -- a workgroup has 256 // cgb slots with cgb <= 32
+#          channel octets, so >= 8 slots share the 256 pixels of a tile: <= 32 additions; the slots are added as a binary tree
+#          over <= 256 slots: 8 levels; mbse_gate_kernel adds the T tiles in four contiguous quarters (ceil(T / 4) additions each),
+#          the four quarters in order (3) and divides once (1).
+#   FC1:   a lane adds channels l, l + 64, ... (ceil(C / 64) fused multiply-adds), a 6-level butterfly, the bias (1).
+#   FC2:   R fused multiply-adds in index order, the bias (1).
+def MBSE_POOL_DEPTH(tiles):
+    return 32 + 8 + (int(tiles) + 3) // 4 + 3 + 1
+
+
+def MBSE_FC1_DEPTH(c):
+    return (int(c) + 63) // 64 + 6 + 1
+
+
+def MBSE_FC2_DEPTH(r):
+    return int(r) + 1
+
+
+MBSE_MAX_C, MBSE_MAX_R = 4096, 1024  # csrc/ssdk_mbse.hip kMbseMaxC / kMbseMaxR (LDS of the gate kernel)
+
+
+class MbSePack(object):
+    """Everything behind the expand 1x1 of one EfficientNet ``MBConvBlock`` (nets/efficientnet.py) packed for
+    ``ssdk_mbse``: depthwise weights [k][k][C] and projection weights [Cout][C] in the activation dtype, their folded
+    BatchNorms and the two squeeze-excite layers ([R][C], [C][R] + biases) in fp32."""
+
+    __slots__ = ("w_dw", "scale_dw", "bias_dw", "w_se1", "b_se1", "w_se2", "b_se2", "w_proj", "scale_proj", "bias_proj",
+                 "cin", "cout", "r", "k", "stride", "residual")
+
+    @staticmethod
+    def _modules(block):
+        _, dw, se, proj, bn = block.parts()
+        se_mods = list(se.se.children())
+        return dw[0], dw[1], dw[2], se_mods, proj, bn
+
+    @staticmethod
+    def supported(block):
+        """The host-side mirror of ssdk_mbse's argument checks (plus the module pattern the pack is built from)."""
+        try:
+            cd, bd, ad, se_mods, cp, bp = MbSePack._modules(block)
+        except (AttributeError, ValueError, IndexError, TypeError):
+            return False
+        if len(se_mods) != 5 or not isinstance(se_mods[0], nn.AdaptiveAvgPool2d) or se_mods[0].output_size not in (1, (1, 1)):
+            return False
+        f1, a1, f2, a2 = se_mods[1:]
+        k, c = cd.kernel_size[0], cd.in_channels
+        return (isinstance(cd, nn.Conv2d) and isinstance(bd, nn.BatchNorm2d) and _act_name(ad) == "silu"
+                and cd.kernel_size in ((3, 3), (5, 5)) and cd.stride in ((1, 1), (2, 2)) and cd.padding == (k // 2, k // 2)
+                and cd.dilation == (1, 1) and cd.padding_mode == "zeros" and cd.bias is None
+                and cd.groups == c == cd.out_channels and c % 8 == 0 and c <= MBSE_MAX_C
+                and all(isinstance(f, nn.Conv2d) and f.kernel_size == (1, 1) and f.stride == (1, 1) and f.padding == (0, 0)
+                        and f.groups == 1 and f.bias is not None for f in (f1, f2))
+                and f1.in_channels == c == f2.out_channels and f1.out_channels == f2.in_channels
+                and 1 <= f1.out_channels <= MBSE_MAX_R and _act_name(a1) == "silu" and _act_name(a2) == "sigmoid"
+                and isinstance(cp, nn.Conv2d) and cp.kernel_size == (1, 1) and cp.stride == (1, 1) and cp.padding == (0, 0)
+                and cp.groups == 1 and cp.in_channels == c and cp.out_channels % 8 == 0 and cp.bias is None
+                and isinstance(bp, nn.BatchNorm2d) and bd.affine and bp.affine)
+
+    def __init__(self, block, dtype):
+        """``dtype``: bfloat16 | float16 for the kernels (folded BN and SE layers then fp32, as ssdk_mbse reads them); float64 keeps
+        every tensor in fp64 (the CPU tests compare the pack with the module at that precision).  The BatchNorms are folded in
+        fp64 either way and rounded once."""
+        cd, bd, _, se_mods, cp, bp = MbSePack._modules(block)
+        f1, f2 = se_mods[1], se_mods[3]
+        aux = torch.float64 if dtype == torch.float64 else torch.float32
+        self.cin, self.cout, self.r = cd.in_channels, cp.out_channels, f1.out_channels
+        self.k, self.stride, self.residual = cd.kernel_size[0], cd.stride[0], bool(block.use_residual)
+
+        def fold(bn):
+            scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+            bias = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+            return scale.to(aux).contiguous(), bias.to(aux).contiguous()
+
+        self.scale_dw, self.bias_dw = fold(bd)
+        self.w_dw = cd.weight.detach()[:, 0].permute(1, 2, 0).contiguous().to(dtype)  # [C,1,k,k] -> [k][k][C]
+        self.w_se1 = f1.weight.detach().reshape(self.r, self.cin).to(aux).contiguous()
+        self.b_se1 = f1.bias.detach().to(aux).contiguous()
+        self.w_se2 = f2.weight.detach().reshape(self.cin, self.r).to(aux).contiguous()
+        self.b_se2 = f2.bias.detach().to(aux).contiguous()
+        self.scale_proj, self.bias_proj = fold(bp)
+        self.w_proj = cp.weight.detach().reshape(self.cout, self.cin).contiguous().to(dtype)
+
+
+def fill_mbse_desc(d, pk, n, h, w, dtype_code, x=None, t=None, pool_partial=None, gate=None, y=None, residual=None, stages=0):
+    d.x, d.t, d.pool_partial, d.gate, d.y, d.residual = x, t, pool_partial, gate, y, residual
+    d.w_dw, d.scale_dw, d.bias_dw = pk.w_dw.data_ptr(), pk.scale_dw.data_ptr(), pk.bias_dw.data_ptr()
+    d.w_se1, d.b_se1, d.w_se2, d.b_se2 = pk.w_se1.data_ptr(), pk.b_se1.data_ptr(), pk.w_se2.data_ptr(), pk.b_se2.data_ptr()
+    d.w_proj, d.scale_proj, d.bias_proj = pk.w_proj.data_ptr(), pk.scale_proj.data_ptr(), pk.bias_proj.data_ptr()
+    d.N, d.H, d.W, d.C, d.R, d.Cout, d.k, d.stride = n, h, w, pk.cin, pk.r, pk.cout, pk.k, pk.stride
+    d.dtype, d.stages = dtype_code, stages
+    return d
+
+
+def mbse_native(x, pk, residual=None, stages=0, t=None, pool_partial=None, gate=None, y=None):
+    """One ``ssdk_mbse`` call on channels_last tensors.  ``stages`` = 0 runs the whole tail; a mask (N.MBSE_DW | MBSE_GATE |
+    MBSE_PROJ) runs those stages on the buffers handed in (the others are allocated).  -> dict(t, pool_partial, gate, y)."""
+    N.require_device(x, "mbse")
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        x = x.contiguous(memory_format=torch.channels_last)
+    n, c, h, w = (int(v) for v in x.shape)
+    ho, wo = _out_hw(h, w, pk.k, pk.stride)
+    tiles = mbse_pool_tiles(h, w, pk.k, pk.stride)
+    dev = x.device
+    t = torch.empty((n, c, ho, wo), device=dev, dtype=x.dtype, memory_format=torch.channels_last) if t is None else t
+    pool_partial = torch.empty((n, tiles, c), device=dev, dtype=torch.float32) if pool_partial is None else pool_partial
+    gate = torch.empty((n, c), device=dev, dtype=torch.float32) if gate is None else gate
+    y = torch.empty((n, pk.cout, ho, wo), device=dev, dtype=x.dtype, memory_format=torch.channels_last) if y is None else y
+    if residual is not None and not residual.is_contiguous(memory_format=torch.channels_last):
+        residual = residual.contiguous(memory_format=torch.channels_last)
+    d = fill_mbse_desc(N.MbSeDesc(), pk, n, h, w, N.dtype_code(x), x.data_ptr(), t.data_ptr(), pool_partial.data_ptr(),
+                       gate.data_ptr(), y.data_ptr(), residual.data_ptr() if residual is not None else None, stages)
+    with torch.cuda.device(dev):
+        rc = N.lib.ssdk_mbse(ctypes.byref(d), N.stream_ptr(dev))
+    N.check(rc, "mbse")
+    STATS["native_layers"] += 1
+    return dict(t=t, pool_partial=pool_partial, gate=gate, y=y)
+
+
 def fill_mb_desc(d, x_ptr, y_ptr, n, h, w, pk, dtype_code):
     d.x, d.y = x_ptr, y_ptr
     d.w_expand, d.scale_expand, d.bias_expand = pk.e.w.data_ptr(), pk.e.scale.data_ptr(), pk.e.bias.data_ptr()
@@ -708,6 +845,25 @@ class ConvPlan(object):
         self.keep.append(pk)
         return (out, n, pk.cout, ho, wo)
 
+    def mbse(self, val, pack, residual=None):
+        """The tail of an EfficientNet MBConv block (``MbSePack``) on ``val`` = the expanded tensor (or the block input of an
+        expand-free block); ``residual``: the block input, added in the projection's epilogue.  t, pool_partial and gate are
+        arena scratch, handed back as soon as the op is recorded (lane 0 ops run in order)."""
+        buf, n, c, h, w = val
+        assert c == pack.cin, (c, pack.cin)
+        ho, wo = _out_hw(h, w, pack.k, pack.stride)
+        if residual is not None:
+            assert tuple(residual[1:]) == (n, pack.cout, ho, wo), (residual[1:], (n, pack.cout, ho, wo))
+        out = self.arena.get(n * pack.cout * ho * wo * self.es)
+        tiles = mbse_pool_tiles(h, w, pack.k, pack.stride)
+        scratch = [self.arena.get(n * c * ho * wo * self.es), self.arena.get(n * tiles * c * 4), self.arena.get(n * c * 4)]
+        self.layers.append(dict(kind="mbse", x=buf, n=n, h=h, w=w, pack=pack, y=out, t=scratch[0], partial=scratch[1],
+                                gate=scratch[2], res=residual[0] if residual is not None else None))
+        for b in scratch:
+            self.arena.release(b)
+        self.keep.append(pack)
+        return (out, n, pack.cout, ho, wo)
+
     def xpair(self, val, p1, p2, lane=0):
         buf, n, c, h, w = val
         assert c == p1.cin, (c, p1.cin)
@@ -809,6 +965,13 @@ class ConvPlan(object):
                 fill_mb_desc(op.mb, self._ptr(L["x"], self.patches, i, "mb.x"), self.arena.ptr(L["y"]), L["n"], L["h"],
                              L["w"], L["pack"], self.dtype_code)
                 continue
+            if kind == "mbse":
+                op.kind = N.OP_MBSE
+                fill_mbse_desc(op.mbse, L["pack"], L["n"], L["h"], L["w"], self.dtype_code,
+                               self._ptr(L["x"], self.patches, i, "mbse.x"), self.arena.ptr(L["t"]), self.arena.ptr(L["partial"]),
+                               self.arena.ptr(L["gate"]), self.arena.ptr(L["y"]),
+                               self._ptr(L["res"], self.patches, i, "mbse.residual") if L["res"] is not None else None)
+                continue
             if kind == "xpair":
                 op.kind = N.OP_XPAIR
                 op.lane = L.get("lane", 0)
@@ -880,6 +1043,14 @@ class ConvPlan(object):
                                  bytes=float(byt), kind="fuse"))
                 continue
             pk, n, h, w = L["pack"], L["n"], L["h"], L["w"]
+            if L.get("kind") == "mbse":  # depthwise + SE + gated projection: x in, y out, t written and read once, the weights
+                ho, wo = _out_hw(h, w, pk.k, pk.stride)
+                macs = n * (ho * wo * pk.k * pk.k * pk.cin + 2 * pk.cin * pk.r + ho * wo * pk.cin * pk.cout)
+                byt = (es * (n * (h * w * pk.cin + 2 * ho * wo * pk.cin + ho * wo * pk.cout) + pk.k * pk.k * pk.cin
+                             + pk.cin * pk.cout) + 4 * (2 * pk.cin * pk.r + pk.r + pk.cin))
+                rows.append(dict(name="mbse %d>%d k%d s%d @%dx%d" % (pk.cin, pk.cout, pk.k, pk.stride, h, w), flops=2.0 * macs,
+                                 bytes=float(byt), kind="mbconv"))
+                continue
             if L.get("kind") == "xpair":
                 p2 = L["pack2"]
                 ho, wo = _out_hw(h, w, 3, 2)

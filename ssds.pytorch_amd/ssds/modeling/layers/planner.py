@@ -11,7 +11,7 @@ import torch.nn as nn
 
 import os
 
-from .fused_conv import ConvPack, ConvPlan, MbPack, StemPack, conv_kind, pack_heads, sequential_groups, xpair_supported
+from .fused_conv import ConvPack, ConvPlan, MbPack, MbSePack, StemPack, conv_kind, pack_heads, sequential_groups, xpair_supported
 
 
 class PlanUnsupported(Exception):
@@ -243,15 +243,58 @@ def record_regnet(plan, val, net):
     return outputs
 
 
+def record_efficientnet(plan, val, net):
+    """EfficientNet (nets/efficientnet.py): 3x3/s2 stem + SiLU on the image-stem kernel, then per MBConv block the expand 1x1
+    (SiLU; absent in the first block) as an ordinary conv and everything behind it as ONE mbse op (csrc/ssdk_mbse.hip) whose
+    projection adds the block input in its epilogue.  The stem kernel exists for 16 / 32 / 64 output channels: B0 ... B2; the
+    40- and 48-channel stems of B3 ... B5 are PlanUnsupported (the backbone then runs on PyTorch-ROCm, reported)."""
+    from ssds.modeling.nets.efficientnet import EfficientEx, MBConvBlock
+    from .fused_conv import mbse_enabled
+
+    if not isinstance(net, EfficientEx):
+        raise PlanUnsupported("backbone {} has no planner".format(type(net).__name__))
+    if not mbse_enabled():
+        raise PlanUnsupported("SSDK_MBSE=0: the EfficientNet backbone runs on PyTorch-ROCm")
+    dt = plan.dtype
+    (sconv, sbn, sact), = groups_of(net.conv1)
+    cur = plan.conv(val, _pack(sconv, sbn, sact, dt, kinds=("stem",)))  # (the image is not an arena buffer)
+    outputs = []
+    for j in range(len(net.settings)):
+        level = j + 1
+        if level > max(net.outputs):
+            break
+        for blk in getattr(net, "stage{}".format(level)):
+            if not isinstance(blk, MBConvBlock) or not MbSePack.supported(blk):
+                raise PlanUnsupported("block not covered by ssdk_mbse: {}".format(type(blk).__name__))
+            keep_cur = any(cur is o for o in outputs)
+            expand = blk.parts()[0]
+            mid = cur
+            if expand is not None:
+                (ec, eb, ea), = groups_of(expand)
+                mid = plan.conv(cur, _pack(ec, eb, ea, dt))
+            out = plan.mbse(mid, MbSePack(blk, dt), residual=cur if blk.use_residual else None)
+            if mid is not cur:
+                plan.release(mid)
+            if not keep_cur:
+                plan.release(cur)
+            cur = out
+        if level in net.outputs:
+            outputs.append(cur)
+    return outputs
+
+
 def record_backbone(plan, val, net):
-    """Backbone maps of a planned backbone (MobileNet, ResNet, RegNetX) from the image value; PlanUnsupported
+    """Backbone maps of a planned backbone (MobileNet, ResNet, RegNetX, EfficientNet) from the image value; PlanUnsupported
     otherwise."""
+    from ssds.modeling.nets.efficientnet import EfficientEx
     from ssds.modeling.nets.mobilenet import MobileNetEx
     from ssds.modeling.nets.regnet import RegNet
     from ssds.modeling.nets.resnet import ResNet
 
     if isinstance(net, MobileNetEx):
         return record_mobilenet(plan, val, net)
+    if isinstance(net, EfficientEx):
+        return record_efficientnet(plan, val, net)
     if isinstance(net, ResNet):
         return record_resnet(plan, val, net)
     if isinstance(net, RegNet):

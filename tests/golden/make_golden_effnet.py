@@ -1,0 +1,92 @@
+"""Generate the EfficientNet detector fixtures (tests/golden/net_<case>.npz for cases_effnet.NET_CASES) by running the
+REFERENCE's own classes, like make_golden.gen_nets does for the other backbones.
+
+Run in the build container only (needs the reference checkout and torch CPU):
+
+    python tests/golden/make_golden_effnet.py
+
+The reference's ``ssds/modeling/nets/efficientnet.py`` is imported unmodified (it is self-contained: no third-party
+package).  Nothing in the test-suite imports this file."""
+import importlib
+import os
+import sys
+import types
+import warnings
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+# the reference checkout: SSDS_REFERENCE, or a `reference` directory next to this repository
+REFERENCE = os.environ.get("SSDS_REFERENCE") or os.path.abspath(os.path.join(HERE, "..", "..", "..", "reference"))
+sys.path.insert(0, HERE)
+sys.path.insert(0, REFERENCE)
+warnings.filterwarnings("ignore")
+
+import cases_effnet as cases  # noqa: E402
+
+torch.set_num_threads(1)
+F32 = np.float32
+
+
+def t(x):
+    return torch.from_numpy(np.ascontiguousarray(x))
+
+
+def _reference_nets():
+    """The reference's ``nets`` package star-imports every backbone family (torchvision subclasses); it is registered as an
+    empty namespace and only its efficientnet module is loaded (as make_golden._reference_nets does for the others)."""
+    import tv_shim
+
+    tv_shim.install()
+    import ssds.modeling  # noqa: F401  (the reference's: REFERENCE is first on sys.path)
+
+    pkg = types.ModuleType("ssds.modeling.nets")
+    pkg.__path__ = [os.path.join(REFERENCE, "ssds", "modeling", "nets")]
+    sys.modules["ssds.modeling.nets"] = pkg
+    mod = importlib.import_module("ssds.modeling.nets.efficientnet")
+    return {n: getattr(mod, n) for n in mod.__all__}
+
+
+def gen_nets():
+    from ssds.modeling import ssds as rssds
+
+    rnets = _reference_nets()
+    for name, (seed, head, net, fl, A, C, (B, H, W)) in cases.NET_CASES.items():
+        cls = getattr(rssds, head)
+        nets_outputs, extras, hd = cls.add_extras(feature_layer=fl, mbox=[A] * len(fl[0]), num_classes=C)
+        backbone = rnets[net](outputs=nets_outputs)
+        backbone.url = None  # no network: skip the ImageNet download of initialize()
+        model = cls(backbone=backbone, extras=extras, head=hd, num_classes=C)
+        sd = model.state_dict()
+        spec = [(k, tuple(v.shape)) for k, v in sd.items()]
+        model.load_state_dict({k: t(v) for k, v in cases.seeded_state(spec, seed).items()})
+        x = t(cases.net_image(name))
+        for m in model.modules():  # BatchNorm calibration: cumulative average over two train-mode passes (make_golden.gen_nets)
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.momentum = None
+        model.train()
+        for m in model.modules():  # (drop-connect would make the calibration passes random)
+            if hasattr(m, "drop_connect_rate"):
+                m.drop_connect_rate = 0.0
+        with torch.no_grad():
+            model(x)
+            model(x)
+        model.eval()
+        with torch.no_grad():
+            loc, conf = model(x)
+        out = {"keys": np.array([k for k, _ in spec]), "shapes": np.array([",".join(map(str, s)) for _, s in spec])}
+        for k, v in model.state_dict().items():
+            if k.endswith("running_mean") or k.endswith("running_var"):
+                out["bn/" + k] = v.numpy().astype(F32)
+        for i, (l, c) in enumerate(zip(loc, conf)):
+            out["loc%d" % i], out["conf%d" % i] = l.numpy(), c.numpy()
+        path = os.path.join(HERE, "net_" + name + ".npz")
+        np.savez_compressed(path, **out)
+        print("net", name, "levels", [tuple(l.shape[-2:]) for l in loc], "params", sum(v.numel() for v in sd.values()),
+              "conf std", ["%.3f" % float(c.std()) for c in conf], "loc absmax", "%.2f" % max(float(l.abs().max()) for l in loc),
+              os.path.getsize(path), "bytes")
+
+
+if __name__ == "__main__":
+    gen_nets()
