@@ -520,6 +520,48 @@ int ssdk_stem7x7s2_fwd(const void* x, const float* w, void* y, int N, int Cin, i
 int ssdk_stem7x7s2_wgrad(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int H, int W,
                          int Cout, int dtype, void* stream);
 
+/* The EfficientNet MBConv layers of the TRAINING step (nets/efficientnet.py; csrc/ssdk_mbconvtrain.hip; added without a version
+ * change: new symbols only).  Tensors are NCHW contiguous, SSDK_BF16 | SSDK_F16, 2-byte aligned (16-byte accesses only where the
+ * address allows); fp32 arithmetic, ONE rounding on every 16-bit store; no allocation, no synchronisation, no atomics, every sum in
+ * a fixed order (two runs give the same bits); hipGraph-capturable.  SSDK_E_BADARG before any device call for a NULL pointer, a
+ * non-positive size, SSDK_F32, a stride outside {1, 2} or a workspace that is too small; the *_workspace_bytes functions answer 0.
+ *
+ * Depthwise 5x5, pad 2, stride 1 | 2, no bias; H, W are the layer INPUT's size, Ho = (H - 1) / stride + 1:
+ *   ssdk_dwconv5_fwd          x [N, C, H, W], w [C, 1, 5, 5] (tensor dtype) -> y [N, C, Ho, Wo], fp32 accumulation in tap order
+ *   ssdk_dwconv5_bwd_data     dy [N, C, Ho, Wo], w -> dx [N, C, H, W]; stride 2 goes by the parity of the dx pixel (taps {0, 2, 4} or
+ *                             {1, 3} per axis), no zero-inserted tensor
+ *   ssdk_dwconv5_bwd_weight   x, dy -> dw [C, 1, 5, 5] fp32: thread partials through a fixed wave tree to workgroup partials in the
+ *                             workspace (ssdk_dwconv5_bwd_weight_workspace_bytes(N, C, H, W, stride) bytes, 4-byte aligned), which a
+ *                             second kernel adds in index order
+ * SiLU + squeeze-excite as one function of u, the depthwise BatchNorm's output: z = silu(u) g with
+ * g = sigmoid(W2 silu(W1 mean_hw(silu(u)) + b1) + b2); silu(u) is computed in fp32 from the stored u (hardware exp2 / rcp) and never
+ * stored.  W1 [Cr, C], b1 [Cr], W2 [C, Cr], b2 [C] are the fp32 parameters (C <= 4096, Cr <= 1024):
+ *   ssdk_se_pool_fwd     u [N, C, H, W] -> pooled [N, C] fp32 = mean_hw(silu(u)) over the unrounded values
+ *   ssdk_se_gate_fwd     pooled, W1, b1, W2, b2 -> hidden_pre [N, Cr] = W1 pooled + b1, gate [N, C] = g, fp32
+ *   ssdk_se_scale_fwd    u, gate -> z [N, C, H, W]
+ *   ssdk_se_bwd_reduce   u, dz -> dgate_raw [N, C] fp32 = sum_hw dz silu(u)
+ *   ssdk_se_gate_bwd     dgate_raw, gate, pooled, hidden_pre, W1, W2 -> dpool [N, C] (the gradient of pooled) and dW1, db1, dW2, db2 in
+ *                        the parameters' shapes, fp32, summed over the batch in image order; workspace:
+ *                        ssdk_se_gate_bwd_workspace_bytes(N, C, Cr) bytes, 4-byte aligned
+ *   ssdk_se_bwd_apply    u, dz, gate, dpool -> du [N, C, H, W] = (dz g + dpool / HW) silu'(u), silu'(u) = s (1 + u (1 - s)), s = sigmoid(u)
+ * Every stage takes inputs of the caller's own. */
+size_t ssdk_dwconv5_bwd_weight_workspace_bytes(int N, int C, int H, int W, int stride);
+int ssdk_dwconv5_fwd(const void* x, const void* w, void* y, int N, int C, int H, int W, int stride, int dtype, void* stream);
+int ssdk_dwconv5_bwd_data(const void* dy, const void* w, void* dx, int N, int C, int H, int W, int stride, int dtype, void* stream);
+int ssdk_dwconv5_bwd_weight(const void* x, const void* dy, float* dw, void* workspace, size_t workspace_bytes, int N, int C, int H, int W,
+                            int stride, int dtype, void* stream);
+int ssdk_se_pool_fwd(const void* u, float* pooled, int N, int C, int H, int W, int dtype, void* stream);
+int ssdk_se_gate_fwd(const float* pooled, const float* w1, const float* b1, const float* w2, const float* b2, float* hidden_pre,
+                     float* gate, int N, int C, int Cr, void* stream);
+int ssdk_se_scale_fwd(const void* u, const float* gate, void* z, int N, int C, int H, int W, int dtype, void* stream);
+int ssdk_se_bwd_reduce(const void* u, const void* dz, float* dgate_raw, int N, int C, int H, int W, int dtype, void* stream);
+size_t ssdk_se_gate_bwd_workspace_bytes(int N, int C, int Cr);
+int ssdk_se_gate_bwd(const float* dgate_raw, const float* gate, const float* pooled, const float* hidden_pre, const float* w1,
+                     const float* w2, float* dpool, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                     size_t workspace_bytes, int N, int C, int Cr, void* stream);
+int ssdk_se_bwd_apply(const void* u, const void* dz, const float* gate, const float* dpool, void* du, int N, int C, int H, int W,
+                      int dtype, void* stream);
+
 /* The grouped 3x3 convolution of the TRAINING step (RegNetX / ResNeXt bottlenecks: nets/regnet.py, nets/resnet.py; csrc/ssdk_gconvtrain.hip):
  * pad 1, stride 1 | 2, C == groups * gw input and output channels, gw = 4 (an even number of groups) or a multiple of 8 up to 256
  * (16 included).  16-bit tensors (SSDK_BF16 | SSDK_F16), NCHW contiguous in and out, 2-byte aligned; fp32 accumulation; no BatchNorm

@@ -184,6 +184,20 @@ def _load():
     lib.ssdk_stem7x7s2_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.ssdk_stem7x7s2_wgrad.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
     lib.ssdk_stem7x7s2_fwd.restype = lib.ssdk_stem7x7s2_wgrad.restype = i32
+    lib.ssdk_dwconv5_bwd_weight_workspace_bytes.argtypes = [i32] * 5
+    lib.ssdk_dwconv5_bwd_weight_workspace_bytes.restype = sz
+    lib.ssdk_dwconv5_fwd.argtypes = lib.ssdk_dwconv5_bwd_data.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.ssdk_dwconv5_bwd_weight.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
+    lib.ssdk_se_pool_fwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.ssdk_se_gate_fwd.argtypes = [vp] * 7 + [i32, i32, i32, vp]
+    lib.ssdk_se_scale_fwd.argtypes = lib.ssdk_se_bwd_reduce.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.ssdk_se_gate_bwd_workspace_bytes.argtypes = [i32] * 3
+    lib.ssdk_se_gate_bwd_workspace_bytes.restype = sz
+    lib.ssdk_se_gate_bwd.argtypes = [vp] * 12 + [sz, i32, i32, i32, vp]
+    lib.ssdk_se_bwd_apply.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    for _n in ("ssdk_dwconv5_fwd", "ssdk_dwconv5_bwd_data", "ssdk_dwconv5_bwd_weight", "ssdk_se_pool_fwd", "ssdk_se_gate_fwd",
+               "ssdk_se_scale_fwd", "ssdk_se_bwd_reduce", "ssdk_se_gate_bwd", "ssdk_se_bwd_apply"):
+        getattr(lib, _n).restype = i32
     lib.ssdk_gconv3x3_train_prepare.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     lib.ssdk_gconv3x3_train_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.ssdk_gconv3x3_train_dgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
@@ -367,7 +381,7 @@ EXPORTS = ("ssdk_version", "ssdk_struct_size", "ssdk_abi_check", "ssdk_last_erro
            "ssdk_ctx_create", "ssdk_ctx_destroy", "ssdk_ctx_set_tail_stream", "ssdk_ctx_set_side_lane", "ssdk_ctx_set_profiling",
            "ssdk_ctx_get_timings", "ssdk_ctx_set_op_profiling", "ssdk_ctx_get_op_timings", "ssdk_ctx_get_tail_stamps",
            "ssdk_run_ops_ctx", "ssdk_decode_nms_ctx",
-           "ssdk_weight_frag_bytes", "ssdk_conv_workspace_bytes", "ssdk_conv", "ssdk_conv_sequence", "ssdk_mbconv", "ssdk_mbk_image_bytes", "ssdk_mbse", "ssdk_mbse_pool_tiles", "ssdk_mbse_desc_bytes", "ssdk_xpair", "ssdk_fuse", "ssdk_preprocess", "ssdk_augment_desc_bytes", "ssdk_augment_workspace_bytes", "ssdk_augment", "ssdk_dwconv_fwd_stats_workspace_bytes", "ssdk_dwconv_fwd_stats", "ssdk_dwconv_affine_supported", "ssdk_dwconv_fwd_affine", "ssdk_dwconv_bwd_weight_affine", "ssdk_bn_act_train_stats", "ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_stats_workspace_bytes", "ssdk_pw_forward_stats", "ssdk_bn_act_train_fwd_sums", "ssdk_pw_wgrad_workspace_bytes", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3", "ssdk_im2col3x3_folded", "ssdk_col2im3x3_folded", "ssdk_stem3x3s2_wgrad_workspace_bytes", "ssdk_stem3x3s2_fwd", "ssdk_stem3x3s2_wgrad", "ssdk_stem7x7s2_wgrad_workspace_bytes", "ssdk_stem7x7s2_fwd", "ssdk_stem7x7s2_wgrad", "ssdk_gconv3x3_train_prepare", "ssdk_gconv3x3_train_forward", "ssdk_gconv3x3_train_dgrad", "ssdk_gconv3x3_train_wgrad_workspace_bytes", "ssdk_gconv3x3_train_wgrad", "ssdk_conv3x3_train_prepare", "ssdk_conv3x3_train_forward", "ssdk_conv3x3_train_dgrad", "ssdk_conv3x3_train_wgrad_workspace_bytes", "ssdk_conv3x3_train_wgrad", "ssdk_pack_conv3x3", "ssdk_pack_conv3x3_dgrad", "ssdk_concat_nchw_to_nhwc", "ssdk_sgd_step", "ssdk_adam_step", "ssdk_rmsprop_step", "ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data",
+           "ssdk_weight_frag_bytes", "ssdk_conv_workspace_bytes", "ssdk_conv", "ssdk_conv_sequence", "ssdk_mbconv", "ssdk_mbk_image_bytes", "ssdk_mbse", "ssdk_mbse_pool_tiles", "ssdk_mbse_desc_bytes", "ssdk_xpair", "ssdk_fuse", "ssdk_preprocess", "ssdk_augment_desc_bytes", "ssdk_augment_workspace_bytes", "ssdk_augment", "ssdk_dwconv_fwd_stats_workspace_bytes", "ssdk_dwconv_fwd_stats", "ssdk_dwconv_affine_supported", "ssdk_dwconv_fwd_affine", "ssdk_dwconv_bwd_weight_affine", "ssdk_bn_act_train_stats", "ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_stats_workspace_bytes", "ssdk_pw_forward_stats", "ssdk_bn_act_train_fwd_sums", "ssdk_pw_wgrad_workspace_bytes", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3", "ssdk_im2col3x3_folded", "ssdk_col2im3x3_folded", "ssdk_stem3x3s2_wgrad_workspace_bytes", "ssdk_stem3x3s2_fwd", "ssdk_stem3x3s2_wgrad", "ssdk_stem7x7s2_wgrad_workspace_bytes", "ssdk_stem7x7s2_fwd", "ssdk_stem7x7s2_wgrad", "ssdk_dwconv5_bwd_weight_workspace_bytes", "ssdk_dwconv5_fwd", "ssdk_dwconv5_bwd_data", "ssdk_dwconv5_bwd_weight", "ssdk_se_pool_fwd", "ssdk_se_gate_fwd", "ssdk_se_scale_fwd", "ssdk_se_bwd_reduce", "ssdk_se_gate_bwd_workspace_bytes", "ssdk_se_gate_bwd", "ssdk_se_bwd_apply", "ssdk_gconv3x3_train_prepare", "ssdk_gconv3x3_train_forward", "ssdk_gconv3x3_train_dgrad", "ssdk_gconv3x3_train_wgrad_workspace_bytes", "ssdk_gconv3x3_train_wgrad", "ssdk_conv3x3_train_prepare", "ssdk_conv3x3_train_forward", "ssdk_conv3x3_train_dgrad", "ssdk_conv3x3_train_wgrad_workspace_bytes", "ssdk_conv3x3_train_wgrad", "ssdk_pack_conv3x3", "ssdk_pack_conv3x3_dgrad", "ssdk_concat_nchw_to_nhwc", "ssdk_sgd_step", "ssdk_adam_step", "ssdk_rmsprop_step", "ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data",
            "ssdk_dwconv_bwd_weight_workspace_bytes", "ssdk_dwconv_bwd_weight", "ssdk_dwconv_plan", "ssdk_bn_workspace_bytes",
            "ssdk_bn_train_fwd", "ssdk_bn_train_bwd", "ssdk_bn_act_train_fwd", "ssdk_bn_act_train_bwd", "ssdk_bn_sync_local_stats",
            "ssdk_bn_sync_fwd_finalize", "ssdk_bn_act_apply", "ssdk_bn_sync_bwd_local", "ssdk_bn_sync_bwd_apply", "ssdk_conv_stem7", "ssdk_maxpool3x3s2", "ssdk_neck_fuse_fwd", "ssdk_neck_fuse_bwd_workspace_bytes", "ssdk_neck_fuse_bwd",

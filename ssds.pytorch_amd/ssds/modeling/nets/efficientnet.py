@@ -6,9 +6,10 @@ the Sequential indices inside ``conv`` are one lower in the expand-free first bl
 classifier tail (``head_conv``, ``classifier``; reference :191-196) is not instantiated.
 
 Eval on a HIP device runs as a recorded plan (planner.record_efficientnet): the expand 1x1 on the dense kernels, the rest
-of every block -- depthwise k x k, squeeze-excite gate, gated projection -- on csrc/ssdk_mbse.hip.  Training keeps these
-layers on the existing paths: the 3x3 depthwise convolutions and the BatchNorms on their kernels, the 5x5 depthwise and
-the squeeze-excite convolutions on PyTorch-ROCm."""
+of every block -- depthwise k x k, squeeze-excite gate, gated projection -- on csrc/ssdk_mbse.hip.  In the training step
+the 3x3 depthwise convolutions, the 1x1 convolutions and the BatchNorms run on their kernels through the Solver's class swaps;
+the 5x5 depthwise convolution and SiLU + squeeze-excite run on csrc/ssdk_mbconvtrain.hip through a swap of the BLOCK's class
+(layers/mbconvtrain.py), so these modules stay what they are."""
 import math
 
 import torch
@@ -28,7 +29,8 @@ class Swish(nn.SiLU):
 
 class PlainConv2d(nn.Conv2d):
     """An ``nn.Conv2d`` that the training Solver's class swaps (``type(m) is nn.Conv2d``) pass over: the 5x5 depthwise
-    convolutions and the squeeze-excite convolutions on 1x1 maps have no training kernels here and stay on PyTorch-ROCm."""
+    convolutions and the squeeze-excite convolutions on 1x1 maps.  Their training kernels are reached through the block
+    (layers/mbconvtrain.TrainMBConvBlock reads these modules' parameters); called as modules they run on PyTorch-ROCm."""
 
 
 class ConvBNReLU(nn.Sequential):

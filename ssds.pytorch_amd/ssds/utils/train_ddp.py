@@ -90,6 +90,13 @@ class Solver(object):
             # the 7x7 / stride-2 stem of the ResNet / ResNeXt backbones (any detector on them): forward + weight gradient on
             # csrc/ssdk_stem7train.hip.  SSDK_STEM7_TRAIN=0: nn.Conv2d, i.e. the library convolution behind autocast's weight cast
             stemconv.use_native_stem7(self.model)
+        from ssds.modeling.layers import mbconvtrain
+
+        if mbconvtrain.enabled():
+            # the EfficientNet MBConv blocks: 5x5 depthwise forward / gradients and SiLU + squeeze-excite on csrc/ssdk_mbconvtrain.hip,
+            # swapped at block level (the convolution modules keep their classes).  SSDK_MBCONV_TRAIN=0: MBConvBlock.forward, i.e.
+            # the library's depthwise kernels and the eager SiLU / pool / 1x1 / multiply passes.  Any model: others have no such block
+            mbconvtrain.use_native_mbconv(self.model)
         from ssds.modeling.layers.headconv import use_head_pairs
 
         use_head_pairs(self.model)  # SSD heads: forward of each level's loc | conf pair on the inference kernels (SSDK_HEAD_PAIR=0: MIOpen)
