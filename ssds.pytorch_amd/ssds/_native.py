@@ -5,387 +5,226 @@ Tensors are passed as raw ``data_ptr()`` values plus the caller's current HIP st
 asynchronous and hipGraph-capturable.  This module is the `ssds._C` the reference names but never
 ships (reference ssds/modeling/layers/box.py:3-4, 419-421, 483-485).
 """
+import collections
 import ctypes
 import os
+import re
 import threading
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "csrc", "libssdk.so")
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "ssdk.h")
 
-MAX_LEVELS = 8
-MAX_ANCHORS = 16
-MAX_TOPN = 1024
-MAX_NDET = 1024
-MAX_NMS_N = 8192
-MAX_GT = 256
+# ---- include/ssdk.h is the one description of the C ABI: prototypes, descriptor structs and constants are read from it ----
 
-F32, BF16, F16 = 0, 1, 2
-ACT = {"none": 0, "relu": 1, "relu6": 2, "silu": 3, "sigmoid": 4}
+Header = collections.namedtuple("Header", "constants structs functions")
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_FIELDS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+_POINTER = re.compile(r"([A-Za-z_][\w ]*?)\s*(\*[\s*]*)([A-Za-z_]\w*)?$")  # pointee words, stars, optional name
+_SCALAR = re.compile(r"(\w+)(?:\s+[A-Za-z_]\w*)?$")  # type word, optional name: `float x[4]` (a pointer in C) does not match
+
+
+def _refuse(what, decl):
+    raise ImportError("include/ssdk.h: {} in `{}` -- ssds/_native.py binds the types of its whitelist only".format(
+        what, " ".join(decl.split())))
+
+
+def _param_type(text, structs, decl):
+    """ctypes type of one parameter (`const float* w`, `size_t n`, `const ssdk_level* levels`)."""
+    text = re.sub(r"\bconst\b", " ", text).strip()
+    m = _POINTER.match(text)
+    if m:
+        pointee = " ".join(m.group(1).split())
+        if pointee in structs and m.group(2).count("*") == 1:
+            return ctypes.POINTER(structs[pointee])
+        return ctypes.c_void_p
+    m = _SCALAR.match(text)
+    if not m or m.group(1) not in _SCALARS:
+        _refuse("parameter `{}` has no ctypes counterpart".format(text), decl)
+    return _SCALARS[m.group(1)]
+
+
+def _return_type(text, opaque, decl):
+    text = " ".join(re.sub(r"\bconst\b", " ", text).replace("*", " * ").split())
+    if text in ("int", "size_t"):
+        return _SCALARS[text]
+    if text == "void":
+        return None
+    if text == "char *":
+        return ctypes.c_char_p
+    if text.endswith(" *") and text[:-2] in opaque:
+        return ctypes.c_void_p
+    _refuse("return type `{}` has no ctypes counterpart".format(text), decl)
+
+
+def _struct_fields(body, constants, structs, decl):
+    fields = []
+    for member in filter(None, (m.strip() for m in body.split(";"))):
+        text = re.sub(r"\bconst\b", " ", member).strip()
+        m = _POINTER.match(text)
+        if m:
+            if not m.group(3):
+                _refuse("member `{}` has no name".format(member), decl)
+            fields.append((m.group(3), ctypes.c_void_p))
+            continue
+        ctype, _, names = text.partition(" ")
+        base = _FIELDS.get(ctype) or structs.get(ctype)
+        if base is None or not names.strip():
+            _refuse("member `{}` has no ctypes counterpart".format(member), decl)
+        for name in names.split(","):
+            m = re.match(r"\s*(\w+)\s*(?:\[\s*(?:(SSDK_\w+)\s*\*\s*)?(\d+)\s*\])?\s*$", name)
+            if not m or (m.group(2) and m.group(2) not in constants):
+                _refuse("member `{}` has a declarator outside `name` / `name[N]` / `name[SSDK_X * N]`".format(member), decl)
+            if m.group(3) is None:
+                fields.append((m.group(1), base))
+            else:
+                fields.append((m.group(1), base * (constants.get(m.group(2), 1) * int(m.group(3)))))
+    return fields
+
+
+def parse_header(text, struct_names=None):
+    """The C ABI that header text declares: ``constants`` {SSDK_X: int} from the #defines and the enums (decimal integers),
+    ``structs`` {typedef name: ctypes.Structure} (class names from ``struct_names``, else the typedef's) and ``functions``
+    {name: (restype, argtypes)}, each in header order.  Anything the closed type whitelist cannot express is an ImportError
+    quoting the declaration -- never skipped, never defaulted: a wrong width here is a truncated device address."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants, structs, functions, opaque = {}, collections.OrderedDict(), collections.OrderedDict(), set()
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SSDK_\w+)(.*)$", text, flags=re.M):
+        if value.strip():  # the include guard has none
+            if not re.match(r"\s+-?\d+\s*$", value):
+                _refuse("the value is not a decimal integer", "#define " + name + value)
+            constants[name] = int(value)
+    text = re.sub(r"#\s*ifdef\s+__cplusplus.*?#\s*endif", " ", text, flags=re.S)  # extern "C" { ... }
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def enum(m):
+        for entry in filter(None, (e.strip() for e in m.group(1).split(","))):
+            e = re.match(r"(SSDK_\w+)\s*=\s*(-?\d+)$", entry)
+            if not e:
+                _refuse("enumerator `{}` has no literal value".format(entry), m.group(0))
+            constants[e.group(1)] = int(e.group(2))
+        return " "
+
+    text = re.sub(r"(?:typedef\s+)?enum\s*\{([^}]*)\}\s*\w*\s*;", enum, text)
+
+    def opaque_struct(m):
+        opaque.add(m.group(1))
+        return " "
+
+    text = re.sub(r"typedef\s+struct\s+\w+\s+(\w+)\s*;", opaque_struct, text)
+    # structs and prototypes in one pass, in header order: a prototype may only point to a struct defined above it
+    pos = 0
+    for m in re.finditer(r"typedef\s+struct\s+\w*\s*\{([^}]*)\}\s*(\w+)\s*;|([^;{}]*[^;{}\s][^;{}]*);", text):
+        if text[pos:m.start()].strip():
+            _refuse("text that is neither a declaration nor a typedef", text[pos:m.start()])
+        pos = m.end()
+        decl = m.group(0)
+        if m.group(2):
+            cname = m.group(2)
+            structs[cname] = type((struct_names or {}).get(cname, cname), (ctypes.Structure,),
+                                  {"_fields_": _struct_fields(m.group(1), constants, structs, decl)})
+            continue
+        f = re.match(r"\s*(.*?)\b(ssdk_\w+)\s*\((.*)\)\s*$", m.group(3), flags=re.S)
+        if not f or not f.group(1).strip():
+            _refuse("not a function prototype", decl)
+        params = f.group(3).strip()
+        functions[f.group(2)] = (_return_type(f.group(1), opaque, decl),
+                                 [] if params == "void" else [_param_type(p, structs, decl) for p in params.split(",")])
+    if text[pos:].strip():
+        _refuse("text that is neither a declaration nor a typedef", text[pos:])
+    return Header(constants, structs, functions)
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError("include/ssdk.h not found at {} -- ssds/_native.py reads the C ABI of libssdk.so from it".format(HEADER_PATH))
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read(), _MIRRORS)
+
+
+# typedef name in the header -> the mirror's name here
+_MIRRORS = collections.OrderedDict((
+    ("ssdk_level", "Level"), ("ssdk_conv_desc", "ConvDesc"), ("ssdk_mbconv_desc", "MbConvDesc"), ("ssdk_fuse_desc", "FuseDesc"),
+    ("ssdk_stem_desc", "StemDesc"), ("ssdk_pool_desc", "PoolDesc"), ("ssdk_xpair_desc", "XpairDesc"),
+    ("ssdk_augment_desc", "AugmentDesc"), ("ssdk_mbse_desc", "MbSeDesc"), ("ssdk_op", "Op")))
+# the library first: without it nothing below matters, and its message says how to build it -- no header error may mask it
+if not os.path.exists(LIB_PATH):
+    raise ImportError(
+        "libssdk.so not found at {} -- build it first: `python -c 'import __graft_entry__ as g; "
+        "g.build()'` or `make -C ssds.pytorch_amd/csrc` (there is no CPU fallback)".format(LIB_PATH)
+    )
+_H = _read_header()
+_K = _H.constants
+
+ABI_VERSION = _K["SSDK_VERSION"]  # a library of an older version is refused by _load
+EXPORTS = tuple(_H.functions)
+
+MAX_LEVELS, MAX_ANCHORS, MAX_TOPN, MAX_NDET, MAX_NMS_N, MAX_GT = (
+    _K["SSDK_MAX_" + n] for n in ("LEVELS", "ANCHORS", "TOPN", "NDET", "NMS_N", "GT"))
+F32, BF16, F16 = _K["SSDK_F32"], _K["SSDK_BF16"], _K["SSDK_F16"]
+ACT = {n: _K["SSDK_ACT_" + n.upper()] for n in ("none", "relu", "relu6", "silu", "sigmoid")}
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
-U8 = 3  # ssdk_preprocess source only
+U8 = _K["SSDK_U8"]  # ssdk_preprocess source only
+OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE = (
+    _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE"))
+MBSE_DW, MBSE_GATE, MBSE_PROJ = 1, 2, 4  # ssdk_mbse_desc.stages bits (0 = all three); the header has no names for them
+FUSE_SAME, FUSE_UP2, FUSE_POOL2 = _K["SSDK_FUSE_SAME"], _K["SSDK_FUSE_UP2"], _K["SSDK_FUSE_POOL2"]
+NCHW, NHWC = _K["SSDK_LAYOUT_NCHW"], _K["SSDK_LAYOUT_NHWC"]
 
-
-class Level(ctypes.Structure):
-    _fields_ = [
-        ("cls", ctypes.c_void_p),
-        ("box", ctypes.c_void_p),
-        ("A", ctypes.c_int32),
-        ("C", ctypes.c_int32),
-        ("H", ctypes.c_int32),
-        ("W", ctypes.c_int32),
-        ("stride", ctypes.c_int32),
-        ("anchors", ctypes.c_float * (MAX_ANCHORS * 4)),
-    ]
-
-
-class ConvDesc(ctypes.Structure):
-    _fields_ = [
-        ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-        ("residual", ctypes.c_void_p), ("y", ctypes.c_void_p), ("y2", ctypes.c_void_p),
-        ("N", ctypes.c_int32), ("Cin", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
-        ("Cout", ctypes.c_int32), ("k", ctypes.c_int32), ("stride", ctypes.c_int32), ("groups", ctypes.c_int32),
-        ("act", ctypes.c_int32), ("act2", ctypes.c_int32), ("split", ctypes.c_int32),
-        ("dtype", ctypes.c_int32), ("in_layout", ctypes.c_int32), ("out_layout", ctypes.c_int32),
-        ("res_mode", ctypes.c_int32), ("w_frag", ctypes.c_void_p),
-    ]
-
-
-class MbConvDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in (
-        "x", "y", "w_expand", "scale_expand", "bias_expand", "w_dw", "bias_dw", "w_project",
-        "scale_project", "bias_project")] + [(n, ctypes.c_int32) for n in (
-            "N", "H", "W", "Cin", "Chid", "Cout", "stride", "residual", "dtype", "stem", "variant",
-            "image_nw")] + [("w_image", ctypes.c_void_p), ("w_image_bytes", ctypes.c_size_t)]
-
-
-class FuseDesc(ctypes.Structure):
-    _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p), ("y", ctypes.c_void_p),
-                ("w0", ctypes.c_float), ("w1", ctypes.c_float), ("w2", ctypes.c_float),
-                ("mode_b", ctypes.c_int32), ("mode_c", ctypes.c_int32),
-                ("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32),
-                ("hb", ctypes.c_int32), ("wb", ctypes.c_int32), ("hc", ctypes.c_int32), ("wc", ctypes.c_int32),
-                ("dtype", ctypes.c_int32)]
-
-
-class StemDesc(ctypes.Structure):
-    _fields_ = [("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("y", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in (
-                    "N", "H", "W", "Cin", "Cout", "act", "dtype", "in_layout")]
-
-
-class PoolDesc(ctypes.Structure):
-    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in (
-        "N", "H", "W", "C", "dtype", "pad")]
-
-
-class XpairDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "y", "w1", "scale1", "bias1", "w2", "scale2", "bias2")] + [
-        (n, ctypes.c_int32) for n in ("N", "H", "W", "Cin", "Cmid", "Cout", "act1", "act2", "dtype", "pad")] + [
-        ("w1_frag", ctypes.c_void_p), ("w2_frag", ctypes.c_void_p)]
-
-
-class AugmentDesc(ctypes.Structure):
-    """ssdk_augment_desc: one image of an ssdk_augment batch (ssds/dataset/augment.py DESC_DTYPE is the numpy view of it)."""
-    _fields_ = [("src_offset", ctypes.c_int64)] + [(n, ctypes.c_int32) for n in (
-        "src_h", "src_w", "crop_x", "crop_y", "crop_w", "crop_h", "canvas_w", "canvas_h", "paste_x", "paste_y", "flip")] + [
-        ("color", ctypes.c_float * 12), ("fill", ctypes.c_float * 3)]
-
-
-class MbSeDesc(ctypes.Structure):
-    """ssdk_mbse_desc: the tail of an EfficientNet MBConv block (depthwise + SE gate + gated projection)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in (
-        "x", "t", "pool_partial", "gate", "y", "residual", "w_dw", "scale_dw", "bias_dw", "w_se1", "b_se1", "w_se2", "b_se2",
-        "w_proj", "scale_proj", "bias_proj")] + [(n, ctypes.c_int32) for n in (
-            "N", "H", "W", "C", "R", "Cout", "k", "stride", "dtype", "stages")]
-
-
-class Op(ctypes.Structure):
-    _fields_ = [("kind", ctypes.c_int32), ("lane", ctypes.c_int32), ("conv", ConvDesc), ("mb", MbConvDesc),
-                ("fuse", FuseDesc), ("stem", StemDesc), ("pool", PoolDesc), ("xpair", XpairDesc), ("mbse", MbSeDesc)]
-
-
-OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE = 0, 1, 2, 3, 4, 5, 6
-MBSE_DW, MBSE_GATE, MBSE_PROJ = 1, 2, 4  # ssdk_mbse_desc.stages bits (0 = all three)
-FUSE_SAME, FUSE_UP2, FUSE_POOL2 = 0, 1, 2
-NCHW, NHWC = 0, 1
-
-
-ABI_VERSION = 245  # include/ssdk.h SSDK_VERSION this module's ctypes mirrors and prototypes are written for
+Level, ConvDesc, MbConvDesc, FuseDesc, StemDesc, PoolDesc, XpairDesc, AugmentDesc, MbSeDesc, Op = (
+    _H.structs[cname] for cname in _MIRRORS)
+AugmentDesc.__doc__ = ("ssdk_augment_desc: one image of an ssdk_augment batch (ssds/dataset/augment.py DESC_DTYPE is the numpy "
+                       "view of it).")
+MbSeDesc.__doc__ = "ssdk_mbse_desc: the tail of an EfficientNet MBConv block (depthwise + SE gate + gated projection)."
 
 
 def _load():
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "libssdk.so not found at {} -- build it first: `python -c 'import __graft_entry__ as g; "
-            "g.build()'` or `make -C ssds.pytorch_amd/csrc` (there is no CPU fallback)".format(LIB_PATH)
-        )
     lib = ctypes.CDLL(LIB_PATH)
-    c = ctypes
-    vp, i32, f32, sz = c.c_void_p, c.c_int, c.c_float, c.c_size_t
-    lib.ssdk_version.restype = i32
-    # version FIRST (ADVICE round 5): a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from
-    # the symbol lookup below would hide what is wrong
+
+    def bind(name):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _H.functions[name]
+        return fn
+
+    # version FIRST: a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from the symbol lookup
+    # below would hide what is wrong
     try:
-        have = int(lib.ssdk_version())
+        have = int(bind("ssdk_version")())
     except AttributeError:
         have = 0
     if have < ABI_VERSION:
         raise ImportError("libssdk.so at {} is ABI {} but ssds/_native.py is written for ABI {}: rebuild it "
                           "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, have, ABI_VERSION))
-    lib.ssdk_struct_size.argtypes = [i32]
-    lib.ssdk_struct_size.restype = sz
-    # the ctypes mirrors below must have the layout the library was BUILT with: a shorter struct would be read past its end
-    for which, cls in enumerate((Level, ConvDesc, MbConvDesc, FuseDesc, StemDesc, PoolDesc, XpairDesc, Op)):
+    for name in EXPORTS:
+        try:
+            bind(name)
+        except AttributeError:
+            raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h declares: rebuild it "
+                              "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, name))
+    # the ctypes mirrors must have the layout the library was BUILT with: a shorter struct would be read past its end.
+    # SSDK_SIZEOF_X is the index of struct ssdk_x
+    for key, which in sorted((kv for kv in _K.items() if kv[0].startswith("SSDK_SIZEOF_")), key=lambda kv: kv[1]):
+        cls = _H.structs["ssdk_" + key[len("SSDK_SIZEOF_"):].lower()]
         want = lib.ssdk_struct_size(which)
         if want != ctypes.sizeof(cls):
             raise ImportError("libssdk.so at {} was built against another include/ssdk.h: sizeof({}) is {} there, {} in ssds/_native.py"
                               .format(LIB_PATH, cls.__name__, want, ctypes.sizeof(cls)))
-    lib.ssdk_last_error.restype = c.c_char_p
-    lib.ssdk_abi_check.argtypes = [i32, sz]
-    lib.ssdk_abi_check.restype = i32
     if lib.ssdk_abi_check(ABI_VERSION, ctypes.sizeof(Op)) != 0:
         raise ImportError("libssdk.so at {}: {}".format(LIB_PATH, lib.ssdk_last_error().decode()))
-    lib.ssdk_last_kernel.restype = c.c_char_p
-    lib.ssdk_mbk_image_bytes.argtypes = [i32] * 6 + [c.POINTER(i32)]
-    lib.ssdk_mbk_image_bytes.restype = sz
-    lib.ssdk_fuse.argtypes = [c.POINTER(FuseDesc), vp]
-    lib.ssdk_fuse.restype = i32
-    lib.ssdk_pw_prepare.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    lib.ssdk_pw_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_pw_stats_workspace_bytes.argtypes = [i32] * 4
-    lib.ssdk_pw_stats_workspace_bytes.restype = sz
-    lib.ssdk_pw_forward_stats.argtypes = [vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_pw_forward_stats.restype = i32
-    lib.ssdk_bn_act_train_fwd_sums.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, f32, f32, i32, i32, vp]
-    lib.ssdk_bn_act_train_fwd_sums.restype = i32
-    lib.ssdk_pw_wgrad_workspace_bytes.argtypes = [i32] * 4
-    lib.ssdk_pw_wgrad_workspace_bytes.restype = sz
-    lib.ssdk_pw_wgrad.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_sgd_step.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, f32, i32, vp, vp]
-    lib.ssdk_sgd_step.restype = i32
-    f64 = c.c_double
-    lib.ssdk_adam_step.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f64, f64, f32, f32, i32, vp, vp]
-    lib.ssdk_adam_step.restype = i32
-    lib.ssdk_rmsprop_step.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, f32, f64, f32, f32, f32, vp, vp]
-    lib.ssdk_rmsprop_step.restype = i32
-    lib.ssdk_im2col3x3.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_col2im3x3.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_im2col3x3_folded.argtypes = lib.ssdk_col2im3x3_folded.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_im2col3x3_folded.restype = lib.ssdk_col2im3x3_folded.restype = i32
-    lib.ssdk_stem3x3s2_wgrad_workspace_bytes.argtypes = [i32, i32]
-    lib.ssdk_stem3x3s2_wgrad_workspace_bytes.restype = sz
-    lib.ssdk_stem3x3s2_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_stem3x3s2_wgrad.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_stem3x3s2_fwd.restype = lib.ssdk_stem3x3s2_wgrad.restype = i32
-    lib.ssdk_stem7x7s2_wgrad_workspace_bytes.argtypes = [i32] * 4
-    lib.ssdk_stem7x7s2_wgrad_workspace_bytes.restype = sz
-    lib.ssdk_stem7x7s2_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_stem7x7s2_wgrad.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_stem7x7s2_fwd.restype = lib.ssdk_stem7x7s2_wgrad.restype = i32
-    lib.ssdk_dwconv5_bwd_weight_workspace_bytes.argtypes = [i32] * 5
-    lib.ssdk_dwconv5_bwd_weight_workspace_bytes.restype = sz
-    lib.ssdk_dwconv5_fwd.argtypes = lib.ssdk_dwconv5_bwd_data.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_dwconv5_bwd_weight.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_se_pool_fwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_se_gate_fwd.argtypes = [vp] * 7 + [i32, i32, i32, vp]
-    lib.ssdk_se_scale_fwd.argtypes = lib.ssdk_se_bwd_reduce.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_se_gate_bwd_workspace_bytes.argtypes = [i32] * 3
-    lib.ssdk_se_gate_bwd_workspace_bytes.restype = sz
-    lib.ssdk_se_gate_bwd.argtypes = [vp] * 12 + [sz, i32, i32, i32, vp]
-    lib.ssdk_se_bwd_apply.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    for _n in ("ssdk_dwconv5_fwd", "ssdk_dwconv5_bwd_data", "ssdk_dwconv5_bwd_weight", "ssdk_se_pool_fwd", "ssdk_se_gate_fwd",
-               "ssdk_se_scale_fwd", "ssdk_se_bwd_reduce", "ssdk_se_gate_bwd", "ssdk_se_bwd_apply"):
-        getattr(lib, _n).restype = i32
-    lib.ssdk_gconv3x3_train_prepare.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    lib.ssdk_gconv3x3_train_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_gconv3x3_train_dgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_gconv3x3_train_wgrad_workspace_bytes.argtypes = [i32] * 6
-    lib.ssdk_gconv3x3_train_wgrad_workspace_bytes.restype = sz
-    lib.ssdk_gconv3x3_train_wgrad.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, vp]
-    for _n in ("ssdk_gconv3x3_train_prepare", "ssdk_gconv3x3_train_forward", "ssdk_gconv3x3_train_dgrad", "ssdk_gconv3x3_train_wgrad"):
-        getattr(lib, _n).restype = i32
-    lib.ssdk_conv3x3_train_prepare.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    lib.ssdk_conv3x3_train_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_conv3x3_train_dgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_conv3x3_train_wgrad_workspace_bytes.argtypes = [i32] * 6
-    lib.ssdk_conv3x3_train_wgrad_workspace_bytes.restype = sz
-    lib.ssdk_conv3x3_train_wgrad.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, vp]
-    for _n in ("ssdk_conv3x3_train_prepare", "ssdk_conv3x3_train_forward", "ssdk_conv3x3_train_dgrad", "ssdk_conv3x3_train_wgrad"):
-        getattr(lib, _n).restype = i32
-    lib.ssdk_neck_fuse_fwd.argtypes = [vp, vp, vp, vp, i32, vp] + [i32] * 11 + [vp]
-    lib.ssdk_neck_fuse_bwd_workspace_bytes.argtypes = [i32] * 4
-    lib.ssdk_neck_fuse_bwd_workspace_bytes.restype = sz
-    lib.ssdk_neck_fuse_bwd.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, sz] + [i32] * 11 + [vp]
-    lib.ssdk_maxpool3x3s2_train_fwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_maxpool3x3s2_train_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    for _n in ("ssdk_neck_fuse_fwd", "ssdk_neck_fuse_bwd", "ssdk_maxpool3x3s2_train_fwd", "ssdk_maxpool3x3s2_train_bwd"):
-        getattr(lib, _n).restype = i32
-    lib.ssdk_pack_conv3x3.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp]
-    lib.ssdk_pack_conv3x3.restype = i32
-    lib.ssdk_pack_conv3x3_dgrad.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]
-    lib.ssdk_pack_conv3x3_dgrad.restype = i32
-    lib.ssdk_concat_nchw_to_nhwc.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]
-    lib.ssdk_concat_nchw_to_nhwc.restype = i32
-    for _n in ("ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3"):
-        getattr(lib, _n).restype = i32
-    lib.ssdk_dwconv_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_dwconv_fwd_stats_workspace_bytes.argtypes = [i32] * 6
-    lib.ssdk_dwconv_fwd_stats_workspace_bytes.restype = sz
-    lib.ssdk_dwconv_fwd_stats.argtypes = [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_dwconv_fwd_stats.restype = i32
-    lib.ssdk_dwconv_affine_supported.argtypes = [i32] * 6
-    lib.ssdk_dwconv_affine_supported.restype = i32
-    lib.ssdk_dwconv_fwd_affine.argtypes = [vp, vp, i32, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_dwconv_fwd_affine.restype = i32
-    lib.ssdk_dwconv_bwd_weight_affine.argtypes = [vp, vp, i32, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_dwconv_bwd_weight_affine.restype = i32
-    lib.ssdk_bn_act_train_stats.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, f32, f32, i32, vp]
-    lib.ssdk_bn_act_train_stats.restype = i32
-    lib.ssdk_dwconv_bwd_data.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_dwconv_bwd_weight_workspace_bytes.argtypes = [i32] * 5
-    lib.ssdk_dwconv_bwd_weight_workspace_bytes.restype = sz
-    lib.ssdk_dwconv_bwd_weight.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_dwconv_plan.argtypes = [i32] * 7 + [ctypes.POINTER(i32)]
-    for _n in ("ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data", "ssdk_dwconv_bwd_weight", "ssdk_dwconv_plan"):
-        getattr(lib, _n).restype = i32
-    lib.ssdk_bn_workspace_bytes.argtypes = [i32, i32]
-    lib.ssdk_bn_workspace_bytes.restype = sz
-    lib.ssdk_bn_train_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, f32, f32, i32, vp]
-    lib.ssdk_bn_train_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]
-    lib.ssdk_bn_act_train_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, f32, f32, i32, i32, vp]
-    lib.ssdk_bn_act_train_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_bn_act_train_fwd.restype = i32
-    lib.ssdk_bn_act_train_bwd.restype = i32
-    lib.ssdk_bn_train_fwd.restype = i32
-    lib.ssdk_bn_train_bwd.restype = i32
-    # synchronised BatchNorm (the split passes around the all-gather: batchnorm._SyncBatchNormTrain)
-    lib.ssdk_bn_sync_local_stats.argtypes = [vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]
-    lib.ssdk_bn_sync_fwd_finalize.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, vp]
-    lib.ssdk_bn_act_apply.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_bn_sync_bwd_local.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, vp]
-    lib.ssdk_bn_sync_bwd_apply.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    for _n in ("ssdk_bn_sync_local_stats", "ssdk_bn_sync_fwd_finalize", "ssdk_bn_act_apply", "ssdk_bn_sync_bwd_local",
-               "ssdk_bn_sync_bwd_apply"):
-        getattr(lib, _n).restype = i32
-    lib.ssdk_preprocess.argtypes = [vp, i32, i32, i32, i32, i32, i32, c.POINTER(f32), c.POINTER(f32), vp, i32, vp]
-    lib.ssdk_preprocess.restype = i32
-    lib.ssdk_conv_stem7.argtypes = [c.POINTER(StemDesc), vp]
-    lib.ssdk_conv_stem7.restype = i32
-    lib.ssdk_maxpool3x3s2.argtypes = [c.POINTER(PoolDesc), vp]
-    lib.ssdk_maxpool3x3s2.restype = i32
-    lib.ssdk_set_op_profiling.argtypes = [i32]
-    lib.ssdk_get_op_timings.argtypes = [c.POINTER(f32), c.POINTER(c.c_char_p), i32]
-    lib.ssdk_device_info.argtypes = [c.POINTER(i32), c.POINTER(i32), c.POINTER(sz), c.c_char_p, i32]
-    lib.ssdk_generate_anchors.argtypes = [i32, c.POINTER(f32), i32, c.POINTER(f32), i32, c.POINTER(f32)]
-    lib.ssdk_decode_workspace_bytes.restype = sz
-    lib.ssdk_decode_workspace_bytes.argtypes = [c.POINTER(Level), i32, i32, i32, i32]
-    lib.ssdk_decode.argtypes = [c.POINTER(Level), i32, i32, f32, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.ssdk_nms_workspace_bytes.restype = sz
-    lib.ssdk_nms_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.ssdk_nms.argtypes = [vp, vp, vp, i32, i32, f32, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.ssdk_decode_nms_workspace_bytes.restype = sz
-    lib.ssdk_decode_nms_workspace_bytes.argtypes = [c.POINTER(Level), i32, i32, i32, i32, i32]
-    lib.ssdk_decode_nms.argtypes = [c.POINTER(Level), i32, i32, i32, f32, i32, i32, f32, i32, i32,
-                                    vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.ssdk_match_targets.argtypes = [vp, i32, i32, c.POINTER(f32), i32, i32, i32, i32, i32, f32, f32,
-                                       f32, vp, vp, vp, vp]
-    lib.ssdk_match_targets_by_scale.argtypes = [vp, i32, i32, c.POINTER(f32), i32, i32, i32, i32, i32, f32,
-                                                f32, i32, vp, vp, vp, vp]
-    lib.ssdk_match_loss_workspace_bytes.restype = sz
-    lib.ssdk_match_loss_workspace_bytes.argtypes = [i32] * 4
-    lib.ssdk_match_loss.restype = i32
-    lib.ssdk_match_loss.argtypes = [vp, i32, i32, c.POINTER(f32), i32, i32, i32, i32, i32, i32, f32, f32, f32,
-                                    vp, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp, sz, vp]
-    lib.ssdk_match_multibox_loss_workspace_bytes.restype = sz
-    lib.ssdk_match_multibox_loss_workspace_bytes.argtypes = [i32] * 4
-    lib.ssdk_match_multibox_loss.restype = i32
-    lib.ssdk_match_multibox_loss.argtypes = [vp, i32, i32, c.POINTER(f32), i32, i32, i32, i32, i32, i32, f32, f32, f32,
-                                             vp, vp, i32, f32, f32, i32, vp, vp, vp, vp, sz, vp]
-    lib.ssdk_debug_lds_probe.restype = i32
-    lib.ssdk_debug_lds_probe.argtypes = [vp, vp]
-    lib.ssdk_set_decode_tail_stream.restype = i32
-    lib.ssdk_set_decode_tail_stream.argtypes = [vp]
-    lib.ssdk_ctx_create.restype = vp
-    lib.ssdk_ctx_create.argtypes = []
-    lib.ssdk_ctx_destroy.restype = None
-    lib.ssdk_ctx_destroy.argtypes = [vp]
-    for _n, _a in (("ssdk_ctx_set_tail_stream", [vp, vp]), ("ssdk_ctx_set_side_lane", [vp, i32]),
-                   ("ssdk_ctx_set_profiling", [vp, i32]), ("ssdk_ctx_get_timings", [vp, i32, c.POINTER(f32), i32]),
-                   ("ssdk_ctx_set_op_profiling", [vp, i32]),
-                   ("ssdk_ctx_get_op_timings", [vp, c.POINTER(f32), c.POINTER(c.c_char_p), i32]),
-                   ("ssdk_ctx_get_tail_stamps", [vp, c.POINTER(c.c_ulonglong), i32]),
-                   ("ssdk_run_ops_ctx", [vp, c.POINTER(Op), i32, vp, sz, vp]),
-                   ("ssdk_decode_nms_ctx", [vp, c.POINTER(Level), i32, i32, i32, f32, i32, i32, f32, i32, i32,
-                                            vp, vp, vp, vp, vp, vp, vp, sz, vp])):
-        getattr(lib, _n).restype = i32
-        getattr(lib, _n).argtypes = _a
-    lib.ssdk_map_match.restype = i32
-    lib.ssdk_map_match.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, f32, f32, vp, vp, vp, vp]
-    lib.ssdk_map_average_precision.restype = i32
-    lib.ssdk_map_average_precision.argtypes = [vp, vp, vp, i32, vp, vp]
-    lib.ssdk_weight_frag_bytes.restype = sz
-    lib.ssdk_weight_frag_bytes.argtypes = [i32, i32]
-    lib.ssdk_conv_workspace_bytes.restype = sz
-    lib.ssdk_conv_workspace_bytes.argtypes = [i32] * 8
-    lib.ssdk_conv_bn_act.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                                     vp, vp, sz, vp]
-    lib.ssdk_conv.argtypes = [c.POINTER(ConvDesc), vp, sz, vp]
-    lib.ssdk_conv.restype = i32
-    lib.ssdk_conv_sequence.argtypes = [c.POINTER(ConvDesc), i32, vp, sz, vp]
-    lib.ssdk_conv_sequence.restype = i32
-    lib.ssdk_mbconv.argtypes = [c.POINTER(MbConvDesc), vp]
-    # ssdk_augment_desc is not behind ssdk_struct_size (its indices are part of ABI 245): the library reports its size itself
-    lib.ssdk_augment_desc_bytes.restype = sz
-    lib.ssdk_augment_desc_bytes.argtypes = []
-    if int(lib.ssdk_augment_desc_bytes()) != c.sizeof(AugmentDesc):
-        raise ImportError("libssdk.so at {} has sizeof(ssdk_augment_desc) = {} but ssds/_native.py mirrors it with {} bytes: "
-                          "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, int(lib.ssdk_augment_desc_bytes()),
-                                                                               c.sizeof(AugmentDesc)))
-    # ssdk_mbse_desc is not behind ssdk_struct_size either (its eight indices are pinned): same arrangement
-    lib.ssdk_mbse_desc_bytes.restype = sz
-    lib.ssdk_mbse_desc_bytes.argtypes = []
-    if int(lib.ssdk_mbse_desc_bytes()) != c.sizeof(MbSeDesc):
-        raise ImportError("libssdk.so at {} has sizeof(ssdk_mbse_desc) = {} but ssds/_native.py mirrors it with {} bytes: "
-                          "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, int(lib.ssdk_mbse_desc_bytes()),
-                                                                               c.sizeof(MbSeDesc)))
-    lib.ssdk_mbse.argtypes = [c.POINTER(MbSeDesc), vp]
-    lib.ssdk_mbse.restype = i32
-    lib.ssdk_mbse_pool_tiles.argtypes = [i32] * 4
-    lib.ssdk_mbse_pool_tiles.restype = i32
-    lib.ssdk_augment_workspace_bytes.restype = sz
-    lib.ssdk_augment_workspace_bytes.argtypes = [i32]
-    lib.ssdk_augment.argtypes = [vp, sz, c.POINTER(AugmentDesc), i32, i32, i32, c.POINTER(f32), c.POINTER(f32), vp, i32, vp, sz, vp]
-    lib.ssdk_augment.restype = i32
-    lib.ssdk_mbconv.restype = i32
-    lib.ssdk_xpair.argtypes = [c.POINTER(XpairDesc), vp]
-    lib.ssdk_xpair.restype = i32
-    lib.ssdk_run_ops.argtypes = [c.POINTER(Op), i32, vp, sz, vp]
-    lib.ssdk_run_ops.restype = i32
-    lib.ssdk_set_profiling.argtypes = [i32]
-    lib.ssdk_get_timings.argtypes = [i32, c.POINTER(f32), i32]
-    for name in ("ssdk_set_profiling", "ssdk_get_timings", "ssdk_device_info", "ssdk_generate_anchors", "ssdk_decode", "ssdk_nms",
-                 "ssdk_decode_nms", "ssdk_match_targets", "ssdk_match_targets_by_scale", "ssdk_conv_bn_act"):
-        getattr(lib, name).restype = i32
+    # ssdk_augment_desc and ssdk_mbse_desc are not behind ssdk_struct_size (its eight indices are part of ABI 245): the
+    # library reports their sizes itself
+    for cname, fn in (("ssdk_augment_desc", lib.ssdk_augment_desc_bytes), ("ssdk_mbse_desc", lib.ssdk_mbse_desc_bytes)):
+        if int(fn()) != ctypes.sizeof(_H.structs[cname]):
+            raise ImportError("libssdk.so at {} has sizeof({}) = {} but ssds/_native.py mirrors it with {} bytes: "
+                              "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, cname, int(fn()),
+                                                                                   ctypes.sizeof(_H.structs[cname])))
     return lib
 
 
 lib = _load()
-EXPORTS = ("ssdk_version", "ssdk_struct_size", "ssdk_abi_check", "ssdk_last_error", "ssdk_last_kernel", "ssdk_set_op_profiling", "ssdk_get_op_timings", "ssdk_device_info", "ssdk_generate_anchors",
-           "ssdk_decode_workspace_bytes", "ssdk_decode", "ssdk_nms_workspace_bytes", "ssdk_nms",
-           "ssdk_decode_nms_workspace_bytes", "ssdk_decode_nms", "ssdk_match_targets",
-           "ssdk_match_targets_by_scale", "ssdk_match_loss_workspace_bytes", "ssdk_match_loss",
-           "ssdk_match_multibox_loss_workspace_bytes", "ssdk_match_multibox_loss",
-           "ssdk_map_match", "ssdk_map_average_precision", "ssdk_set_decode_tail_stream", "ssdk_debug_lds_probe",
-           "ssdk_ctx_create", "ssdk_ctx_destroy", "ssdk_ctx_set_tail_stream", "ssdk_ctx_set_side_lane", "ssdk_ctx_set_profiling",
-           "ssdk_ctx_get_timings", "ssdk_ctx_set_op_profiling", "ssdk_ctx_get_op_timings", "ssdk_ctx_get_tail_stamps",
-           "ssdk_run_ops_ctx", "ssdk_decode_nms_ctx",
-           "ssdk_weight_frag_bytes", "ssdk_conv_workspace_bytes", "ssdk_conv", "ssdk_conv_sequence", "ssdk_mbconv", "ssdk_mbk_image_bytes", "ssdk_mbse", "ssdk_mbse_pool_tiles", "ssdk_mbse_desc_bytes", "ssdk_xpair", "ssdk_fuse", "ssdk_preprocess", "ssdk_augment_desc_bytes", "ssdk_augment_workspace_bytes", "ssdk_augment", "ssdk_dwconv_fwd_stats_workspace_bytes", "ssdk_dwconv_fwd_stats", "ssdk_dwconv_affine_supported", "ssdk_dwconv_fwd_affine", "ssdk_dwconv_bwd_weight_affine", "ssdk_bn_act_train_stats", "ssdk_pw_prepare", "ssdk_pw_forward", "ssdk_pw_stats_workspace_bytes", "ssdk_pw_forward_stats", "ssdk_bn_act_train_fwd_sums", "ssdk_pw_wgrad_workspace_bytes", "ssdk_pw_wgrad", "ssdk_im2col3x3", "ssdk_col2im3x3", "ssdk_im2col3x3_folded", "ssdk_col2im3x3_folded", "ssdk_stem3x3s2_wgrad_workspace_bytes", "ssdk_stem3x3s2_fwd", "ssdk_stem3x3s2_wgrad", "ssdk_stem7x7s2_wgrad_workspace_bytes", "ssdk_stem7x7s2_fwd", "ssdk_stem7x7s2_wgrad", "ssdk_dwconv5_bwd_weight_workspace_bytes", "ssdk_dwconv5_fwd", "ssdk_dwconv5_bwd_data", "ssdk_dwconv5_bwd_weight", "ssdk_se_pool_fwd", "ssdk_se_gate_fwd", "ssdk_se_scale_fwd", "ssdk_se_bwd_reduce", "ssdk_se_gate_bwd_workspace_bytes", "ssdk_se_gate_bwd", "ssdk_se_bwd_apply", "ssdk_gconv3x3_train_prepare", "ssdk_gconv3x3_train_forward", "ssdk_gconv3x3_train_dgrad", "ssdk_gconv3x3_train_wgrad_workspace_bytes", "ssdk_gconv3x3_train_wgrad", "ssdk_conv3x3_train_prepare", "ssdk_conv3x3_train_forward", "ssdk_conv3x3_train_dgrad", "ssdk_conv3x3_train_wgrad_workspace_bytes", "ssdk_conv3x3_train_wgrad", "ssdk_pack_conv3x3", "ssdk_pack_conv3x3_dgrad", "ssdk_concat_nchw_to_nhwc", "ssdk_sgd_step", "ssdk_adam_step", "ssdk_rmsprop_step", "ssdk_dwconv_fwd", "ssdk_dwconv_bwd_data",
-           "ssdk_dwconv_bwd_weight_workspace_bytes", "ssdk_dwconv_bwd_weight", "ssdk_dwconv_plan", "ssdk_bn_workspace_bytes",
-           "ssdk_bn_train_fwd", "ssdk_bn_train_bwd", "ssdk_bn_act_train_fwd", "ssdk_bn_act_train_bwd", "ssdk_bn_sync_local_stats",
-           "ssdk_bn_sync_fwd_finalize", "ssdk_bn_act_apply", "ssdk_bn_sync_bwd_local", "ssdk_bn_sync_bwd_apply", "ssdk_conv_stem7", "ssdk_maxpool3x3s2", "ssdk_neck_fuse_fwd", "ssdk_neck_fuse_bwd_workspace_bytes", "ssdk_neck_fuse_bwd",
-           "ssdk_maxpool3x3s2_train_fwd", "ssdk_maxpool3x3s2_train_bwd", "ssdk_run_ops", "ssdk_conv_bn_act", "ssdk_set_profiling", "ssdk_get_timings")
 
 
 class Context(object):
