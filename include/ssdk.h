@@ -908,8 +908,16 @@ int ssdk_mbse(const ssdk_mbse_desc* desc, void* stream);
 int ssdk_mbse_pool_tiles(int H, int W, int k, int stride); /* 0 for arguments ssdk_mbse does not take */
 size_t ssdk_mbse_desc_bytes(void);
 
+/* SSDK_OP_CONVT (executor op kind 7, lane 0 only): the transposed 3x3 / stride 2 / pad 1 convolution + bias (+ skip) of the Shelf
+ * neck, ssdk_convt3x3s2 of include/ssdk_convt.h.  It brings NO member of its own to ssdk_op (the layout, sizeof(ssdk_op) and
+ * SSDK_VERSION stay as they are): the op is described by its `conv` member, read as
+ *   x, y         NHWC input [N][H][W][Cin] and output [N][2H-1][2W-1][Cout] (in_layout = out_layout = SSDK_LAYOUT_NHWC)
+ *   w            the four parity images of the weight (ssdk_convt_desc.w_pack), not a KRSC tensor
+ *   bias         fp32 [Cout] or NULL;  residual = the skip tensor [N][2H-1][2W-1][Cout] or NULL
+ *   N, Cin, H, W, Cout, act, dtype as in ssdk_convt_desc;  k = 3, stride = 2, groups = 1 (anything else: SSDK_E_BADARG)
+ * scale, y2, w_frag must be NULL and res_mode 0. */
 enum { SSDK_OP_CONV = 0, SSDK_OP_MBCONV = 1, SSDK_OP_FUSE = 2, SSDK_OP_STEM7 = 3, SSDK_OP_POOL = 4, SSDK_OP_XPAIR = 5,
-       SSDK_OP_MBSE = 6 /* lane 0 only */ };
+       SSDK_OP_MBSE = 6 /* lane 0 only */, SSDK_OP_CONVT = 7 /* lane 0 only; described by `conv`, see above */ };
 typedef struct ssdk_op {
   int32_t kind, lane;
   ssdk_conv_desc conv;

@@ -26,6 +26,7 @@
 //   y      NHWC [N][Ho][Wo][Cout] or NCHW [N][Cout][Ho][Wo]        same dtype
 #include "ssdk_conv_common.h"
 #include "ssdk_ctx.h"
+#include "../../include/ssdk_convt.h"
 
 namespace ssdk {
 
@@ -1489,6 +1490,21 @@ static bool group_members_independent(const ConvParams& a, const ConvParams& b) 
   return true;
 }
 
+// SSDK_OP_CONVT: the op's ssdk_conv_desc read as a transposed 3x3 / stride 2 convolution (include/ssdk.h) -> ssdk_convt3x3s2
+static int run_convt_op(const ssdk_conv_desc* c, hipStream_t st) {
+  if (c->k != 3 || c->stride != 2 || c->groups > 1 || c->in_layout != LAYOUT_NHWC || c->out_layout != LAYOUT_NHWC || c->scale || c->y2 ||
+      c->w_frag || c->res_mode) {
+    set_error("convt op: k=%d stride=%d groups=%d layouts %d/%d res_mode=%d (k 3, stride 2, groups 1, NHWC in and out, no scale / y2 / "
+              "w_frag / res_mode)", c->k, c->stride, c->groups, c->in_layout, c->out_layout, c->res_mode);
+    return SSDK_E_BADARG;
+  }
+  ssdk_convt_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x = c->x, d.w_pack = c->w, d.bias = c->bias, d.skip = c->residual, d.y = c->y;
+  d.N = c->N, d.Cin = c->Cin, d.H = c->H, d.W = c->W, d.Cout = c->Cout, d.act = c->act, d.dtype = c->dtype;
+  return ssdk_convt3x3s2(&d, st);
+}
+
 extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* workspace, size_t workspace_bytes,
                                 void* stream) {
   if (int rc = ssdk::ctx_enter(ctx)) return rc;
@@ -1593,6 +1609,7 @@ extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* 
       else if (ops[i].kind == SSDK_OP_POOL) rc = ssdk_maxpool3x3s2(&ops[i].pool, st);
       else if (ops[i].kind == SSDK_OP_XPAIR) rc = ssdk_xpair(&ops[i].xpair, st);
       else if (ops[i].kind == SSDK_OP_MBSE && ops[i].lane == 0) rc = ssdk_mbse(&ops[i].mbse, st);
+      else if (ops[i].kind == SSDK_OP_CONVT && ops[i].lane == 0) rc = run_convt_op(&ops[i].conv, st);
       else {
         set_error("unknown op kind %d", ops[i].kind);
         rc = SSDK_E_BADARG;

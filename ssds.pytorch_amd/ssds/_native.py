@@ -168,8 +168,8 @@ F32, BF16, F16 = _K["SSDK_F32"], _K["SSDK_BF16"], _K["SSDK_F16"]
 ACT = {n: _K["SSDK_ACT_" + n.upper()] for n in ("none", "relu", "relu6", "silu", "sigmoid")}
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 U8 = _K["SSDK_U8"]  # ssdk_preprocess source only
-OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE = (
-    _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE"))
+OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE, OP_CONVT = (
+    _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE", "CONVT"))
 MBSE_DW, MBSE_GATE, MBSE_PROJ = 1, 2, 4  # ssdk_mbse_desc.stages bits (0 = all three); the header has no names for them
 FUSE_SAME, FUSE_UP2, FUSE_POOL2 = _K["SSDK_FUSE_SAME"], _K["SSDK_FUSE_UP2"], _K["SSDK_FUSE_POOL2"]
 NCHW, NHWC = _K["SSDK_LAYOUT_NCHW"], _K["SSDK_LAYOUT_NHWC"]
@@ -180,13 +180,25 @@ AugmentDesc.__doc__ = ("ssdk_augment_desc: one image of an ssdk_augment batch (s
                        "view of it).")
 MbSeDesc.__doc__ = "ssdk_mbse_desc: the tail of an EfficientNet MBConv block (depthwise + SE gate + gated projection)."
 
+# include/ssdk_convt.h: the transposed convolution of the Shelf neck.  A header of its own -- the entry points of ssdk.h and the
+# layout of ssdk_op are a closed list under ABI 245 -- read with the same parser; its entry points are bound next to EXPORTS.
+CONVT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_convt.h")
+if not os.path.exists(CONVT_HEADER_PATH):
+    raise ImportError("include/ssdk_convt.h not found at {} -- ssds/_native.py reads the transposed convolution's C ABI from it".format(
+        CONVT_HEADER_PATH))
+with open(CONVT_HEADER_PATH) as _f:
+    _HT = parse_header(_f.read(), {"ssdk_convt_desc": "ConvTDesc"})
+CONVT_EXPORTS = tuple(_HT.functions)
+ConvTDesc = _HT.structs["ssdk_convt_desc"]
+ConvTDesc.__doc__ = "ssdk_convt_desc: transposed 3x3 / stride 2 / pad 1 convolution + bias (+ skip), the Shelf decoder step."
+
 
 def _load():
     lib = ctypes.CDLL(LIB_PATH)
 
     def bind(name):
         fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _H.functions[name]
+        fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions[name])
         return fn
 
     # version FIRST: a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from the symbol lookup
@@ -198,7 +210,7 @@ def _load():
     if have < ABI_VERSION:
         raise ImportError("libssdk.so at {} is ABI {} but ssds/_native.py is written for ABI {}: rebuild it "
                           "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, have, ABI_VERSION))
-    for name in EXPORTS:
+    for name in EXPORTS + CONVT_EXPORTS:
         try:
             bind(name)
         except AttributeError:
@@ -214,13 +226,14 @@ def _load():
                               .format(LIB_PATH, cls.__name__, want, ctypes.sizeof(cls)))
     if lib.ssdk_abi_check(ABI_VERSION, ctypes.sizeof(Op)) != 0:
         raise ImportError("libssdk.so at {}: {}".format(LIB_PATH, lib.ssdk_last_error().decode()))
-    # ssdk_augment_desc and ssdk_mbse_desc are not behind ssdk_struct_size (its eight indices are part of ABI 245): the
+    # ssdk_augment_desc, ssdk_mbse_desc and ssdk_convt_desc (ssdk_convt.h) are not behind ssdk_struct_size (its eight indices are part of ABI 245): the
     # library reports their sizes itself
-    for cname, fn in (("ssdk_augment_desc", lib.ssdk_augment_desc_bytes), ("ssdk_mbse_desc", lib.ssdk_mbse_desc_bytes)):
-        if int(fn()) != ctypes.sizeof(_H.structs[cname]):
+    for cname, fn in (("ssdk_augment_desc", lib.ssdk_augment_desc_bytes), ("ssdk_mbse_desc", lib.ssdk_mbse_desc_bytes),
+                      ("ssdk_convt_desc", lib.ssdk_convt_desc_bytes)):
+        if int(fn()) != ctypes.sizeof(dict(_H.structs, **_HT.structs)[cname]):
             raise ImportError("libssdk.so at {} has sizeof({}) = {} but ssds/_native.py mirrors it with {} bytes: "
                               "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, cname, int(fn()),
-                                                                                   ctypes.sizeof(_H.structs[cname])))
+                                                                                   ctypes.sizeof(dict(_H.structs, **_HT.structs)[cname])))
     return lib
 
 

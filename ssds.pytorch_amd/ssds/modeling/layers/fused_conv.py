@@ -547,6 +547,85 @@ def mbse_native(x, pk, residual=None, stages=0, t=None, pool_partial=None, gate=
     return dict(t=t, pool_partial=pool_partial, gate=gate, y=y)
 
 
+# ---- transposed 3x3 / stride 2 / pad 1 convolution (csrc/ssdk_convt.hip): the decoder step of the Shelf neck ----------------
+def convt_class_taps(py, px):
+    """Taps of output parity class (py, px) = (oy & 1, ox & 1) in image order: [(dy, dx, ky, kx)] -- tap dy * (1 + px) + dx reads
+    input pixel (iy + dy, ix + dx) of output pixel (2 iy + py, 2 ix + px) through weight element [ky][kx] (oy = 2 iy - 1 + ky:
+    an even row takes ky = 1; an odd row ky = 2 from iy and ky = 0 from iy + 1; columns alike)."""
+    return [(dy, dx, 2 - 2 * dy if py else 1, 2 - 2 * dx if px else 1) for dy in range(1 + py) for dx in range(1 + px)]
+
+
+def convt_parity_images(w):
+    """``w``: ConvTranspose2d weight [Cin][Cout][3][3] -> the four parity images of include/ssdk_convt.h ``ssdk_convt_desc.w_pack``
+    (class 2 py + px), each the fragment-major image [ceil(Cout / 16)][Kc / 32][4][16][8] of the matrix [Cout][Kc] with
+    k = tap * Cin + ci and Kc = taps * Cin rounded up to 32 by zeros.  Pure layout, on the tensor's own device and dtype."""
+    cin, cout, kh, kw = (int(v) for v in w.shape)
+    assert kh == 3 and kw == 3, tuple(w.shape)
+    g = (cout + 15) // 16
+    images = []
+    for py in (0, 1):
+        for px in (0, 1):
+            taps = convt_class_taps(py, px)
+            kc = 32 * ((len(taps) * cin + 31) // 32)
+            mat = w.new_zeros((g * 16, kc))
+            for t, (_, _, ky, kx) in enumerate(taps):
+                mat[:cout, t * cin:(t + 1) * cin] = w[:, :, ky, kx].t()
+            images.append(mat.view(g, 16, kc // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous())
+    return images
+
+
+class ConvTPack(object):
+    """``nn.ConvTranspose2d(Cin, Cout, 3, stride=2, padding=1)`` packed for ``ssdk_convt3x3s2``: the four parity images of the
+    weight in the activation dtype, one behind the other, and the fp32 bias (None without one)."""
+
+    __slots__ = ("w", "bias", "cin", "cout")
+
+    @staticmethod
+    def supported(m):
+        """The host-side mirror of ssdk_convt3x3s2's argument checks (plus the module it is built from)."""
+        return (isinstance(m, nn.ConvTranspose2d) and m.kernel_size == (3, 3) and m.stride == (2, 2) and m.padding == (1, 1)
+                and m.output_padding == (0, 0) and m.dilation == (1, 1) and m.groups == 1
+                and m.in_channels % 8 == 0 and m.out_channels % 8 == 0)
+
+    def __init__(self, convt, dtype):
+        if not ConvTPack.supported(convt):
+            raise N.SsdkError("{} is not covered by ssdk_convt3x3s2".format(convt))
+        self.cin, self.cout = convt.in_channels, convt.out_channels
+        self.w = torch.cat([im.reshape(-1) for im in convt_parity_images(convt.weight.detach().to(dtype))]).contiguous()
+        assert self.w.numel() * self.w.element_size() == N.lib.ssdk_convt_pack_bytes(self.cin, self.cout)
+        self.bias = convt.bias.detach().float().contiguous() if convt.bias is not None else None
+
+
+def fill_convt_desc(d, pk, n, h, w, dtype_code, x=None, y=None, skip=None, act="none"):
+    d.x, d.w_pack, d.skip, d.y = x, pk.w.data_ptr(), skip, y
+    d.bias = pk.bias.data_ptr() if pk.bias is not None else None
+    d.N, d.Cin, d.H, d.W, d.Cout, d.act, d.dtype = n, pk.cin, h, w, pk.cout, N.ACT[act], dtype_code
+    return d
+
+
+def convt_native(x, pk, skip=None, act="none", y=None):
+    """One ``ssdk_convt3x3s2`` call: channels_last x [N, Cin, H, W] -> channels_last [N, Cout, 2H - 1, 2W - 1] =
+    act(conv_transpose2d(x) + bias) (+ skip)."""
+    N.require_device(x, "convt3x3s2")
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        x = x.contiguous(memory_format=torch.channels_last)
+    n, c, h, w = (int(v) for v in x.shape)
+    assert c == pk.cin, (c, pk.cin)
+    if y is None:
+        y = torch.empty((n, pk.cout, 2 * h - 1, 2 * w - 1), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    if skip is not None:
+        assert tuple(skip.shape) == tuple(y.shape) and skip.dtype == x.dtype, (tuple(skip.shape), tuple(y.shape))
+        if not skip.is_contiguous(memory_format=torch.channels_last):
+            skip = skip.contiguous(memory_format=torch.channels_last)
+    d = fill_convt_desc(N.ConvTDesc(), pk, n, h, w, N.dtype_code(x), x.data_ptr(), y.data_ptr(),
+                        skip.data_ptr() if skip is not None else None, act)
+    with torch.cuda.device(x.device):
+        rc = N.lib.ssdk_convt3x3s2(ctypes.byref(d), N.stream_ptr(x.device))
+    N.check(rc, "convt3x3s2")
+    STATS["native_layers"] += 1
+    return y
+
+
 def fill_mb_desc(d, x_ptr, y_ptr, n, h, w, pk, dtype_code):
     d.x, d.y = x_ptr, y_ptr
     d.w_expand, d.scale_expand, d.bias_expand = pk.e.w.data_ptr(), pk.e.scale.data_ptr(), pk.e.bias.data_ptr()
@@ -864,6 +943,19 @@ class ConvPlan(object):
         self.keep.append(pack)
         return (out, n, pack.cout, ho, wo)
 
+    def convt(self, val, pack, skip=None):
+        """Transposed 3x3 / stride 2 / pad 1 convolution (``ConvTPack``) + bias (+ ``skip``, a value at the output's size): the
+        decoder step of the Shelf neck as one op, [n, c, h, w] -> [n, cout, 2h - 1, 2w - 1]."""
+        buf, n, c, h, w = val
+        assert c == pack.cin, (c, pack.cin)
+        ho, wo = 2 * h - 1, 2 * w - 1
+        if skip is not None:
+            assert tuple(skip[1:]) == (n, pack.cout, ho, wo), (skip[1:], (n, pack.cout, ho, wo))
+        out = self.arena.get(n * pack.cout * ho * wo * self.es)
+        self.layers.append(dict(kind="convt", x=buf, n=n, h=h, w=w, pack=pack, y=out, res=skip[0] if skip is not None else None))
+        self.keep.append(pack)
+        return (out, n, pack.cout, ho, wo)
+
     def xpair(self, val, p1, p2, lane=0):
         buf, n, c, h, w = val
         assert c == p1.cin, (c, p1.cin)
@@ -972,6 +1064,16 @@ class ConvPlan(object):
                                self.arena.ptr(L["gate"]), self.arena.ptr(L["y"]),
                                self._ptr(L["res"], self.patches, i, "mbse.residual") if L["res"] is not None else None)
                 continue
+            if kind == "convt":  # carried by the op's ssdk_conv_desc (include/ssdk.h SSDK_OP_CONVT): w = the parity images
+                op.kind = N.OP_CONVT
+                c, pk = op.conv, L["pack"]
+                c.x, c.w, c.y = self._ptr(L["x"], self.patches, i, "conv.x"), pk.w.data_ptr(), self.arena.ptr(L["y"])
+                c.bias = pk.bias.data_ptr() if pk.bias is not None else None
+                c.residual = self._ptr(L["res"], self.patches, i, "conv.residual") if L["res"] is not None else None
+                c.N, c.Cin, c.H, c.W, c.Cout, c.k, c.stride, c.groups = L["n"], pk.cin, L["h"], L["w"], pk.cout, 3, 2, 1
+                c.act = c.act2 = N.ACT["none"]
+                c.split, c.dtype, c.in_layout, c.out_layout = pk.cout, self.dtype_code, N.NHWC, N.NHWC
+                continue
             if kind == "xpair":
                 op.kind = N.OP_XPAIR
                 op.lane = L.get("lane", 0)
@@ -1050,6 +1152,13 @@ class ConvPlan(object):
                              + pk.cin * pk.cout) + 4 * (2 * pk.cin * pk.r + pk.r + pk.cin))
                 rows.append(dict(name="mbse %d>%d k%d s%d @%dx%d" % (pk.cin, pk.cout, pk.k, pk.stride, h, w), flops=2.0 * macs,
                                  bytes=float(byt), kind="mbconv"))
+                continue
+            if L.get("kind") == "convt":  # 9 taps per 2 x 2 output quad, less the last row / column's; x, skip, y and the weights once
+                macs = n * pk.cin * pk.cout * (h * w + 2 * h * (w - 1) + 2 * (h - 1) * w + 4 * (h - 1) * (w - 1))
+                ho, wo = 2 * h - 1, 2 * w - 1
+                byt = es * (n * (h * w * pk.cin + (2 if L["res"] is not None else 1) * ho * wo * pk.cout) + 9 * pk.cin * pk.cout)
+                rows.append(dict(name="convt %d>%d k3 s2 @%dx%d" % (pk.cin, pk.cout, h, w), flops=2.0 * macs, bytes=float(byt),
+                                 kind="conv"))
                 continue
             if L.get("kind") == "xpair":
                 p2 = L["pack2"]

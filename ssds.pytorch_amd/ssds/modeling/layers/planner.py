@@ -3,15 +3,15 @@ group becomes one descriptor of the fused HIP kernels, block-level residual adds
 the projecting 1x1 conv, and the loc | conf convs of each level become one split-output GEMM.
 
 Covered: MobileNet v1/v2 backbones (nets/mobilenet.py), the SSD extras and heads (ssds/ssd.py) -- i.e. the
-network of BASELINE configs 1, 2 and 4 -- and the FPN / BiFPN necks with their shared towers (ssds/fpn.py,
-ssds/bifpn.py; configs 3 and 5) on top of backbone feature maps handed in as external inputs.  Anything else
+network of BASELINE configs 1, 2 and 4 -- and the FPN / BiFPN / Shelf necks with their towers or heads (ssds/fpn.py,
+ssds/bifpn.py, ssds/shelf.py; configs 3 and 5) on top of backbone feature maps handed in as external inputs.  Anything else
 raises ``PlanUnsupported`` and the caller runs the module-by-module path instead (and says so in
 ``fused_conv.STATS``)."""
 import torch.nn as nn
 
 import os
 
-from .fused_conv import ConvPack, ConvPlan, MbPack, MbSePack, StemPack, conv_kind, pack_heads, sequential_groups, xpair_supported
+from .fused_conv import ConvPack, ConvPlan, ConvTPack, MbPack, MbSePack, StemPack, conv_kind, pack_heads, sequential_groups, xpair_supported
 
 
 class PlanUnsupported(Exception):
@@ -453,4 +453,83 @@ def build_bifpn_plan(model, features=None, image=None):
     for m in model.stack_bifpn:
         xx = _record_bifpn_layer(plan, m, xx)
     _record_extras_and_towers(plan, model, xx, vals[n - 1])
+    return plan.finalize()
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Shelf neck + per-level heads (ssds/shelf.py)
+# --------------------------------------------------------------------------------------------------------------
+def _record_shared_block(plan, blk, x):
+    """SharedBlock (reference shelf.py:10-35): ONE 3x3 weight, two launches -- BatchNorm 1 + ReLU, then BatchNorm 2 + x and the
+    ReLU behind the add (res_mode bit 1, as the ResNet blocks).  The Dropout2d between them is the identity in eval."""
+    from ssds.modeling.ssds.shelf import SharedBlock
+
+    if not isinstance(blk, SharedBlock) or blk.conv1.out_channels % 8:
+        raise PlanUnsupported("block {} has no planner".format(type(blk).__name__))
+    mid = plan.conv(x, _pack(blk.conv1, blk.bn1, "relu", plan.dtype))
+    out = plan.conv(mid, _pack(blk.conv1, blk.bn2, "relu", plan.dtype), residual=x, res_mode=2)
+    plan.release(mid)
+    return out
+
+
+def _record_shelf_pyramid(plan, pyr, xx):
+    """ShelfPyramid (reference shelf.py:38-62) on the values ``xx``: block0 on the first, then per level
+    block_i(conv_i(previous) + xx[i]) with the add in conv_i's epilogue -- a transposed convolution (decoder: one ssdk_convt op)
+    or a ConvBNReLU / stride 2 (encoder: ReLU before the add, res_mode 0).  Returns the levels reversed, like the module; the
+    inputs are handed back to the arena."""
+    out, x = [], xx[0]
+    for i in range(len(xx)):
+        if i > 0:
+            m = getattr(pyr, "conv{}".format(i))
+            if isinstance(m, nn.ConvTranspose2d):
+                if not ConvTPack.supported(m):
+                    raise PlanUnsupported("transposed conv not covered by ssdk_convt3x3s2: {}".format(m))
+                x = plan.convt(x, ConvTPack(m, plan.dtype), skip=xx[i])
+            else:
+                (conv, bn, act), = groups_of(m)
+                if conv.kernel_size != (3, 3) or conv.stride != (2, 2) or conv.out_channels % 8:
+                    raise PlanUnsupported("encoder step not covered: {}".format(conv))
+                x = plan.conv(x, _pack(conv, bn, act, plan.dtype), residual=xx[i])
+        blk_in = x
+        x = _record_shared_block(plan, getattr(pyr, "block{}".format(i)), blk_in)
+        if i > 0:
+            plan.release(blk_in)
+        out.append(x)
+    for v in xx:
+        plan.release(v)
+    return out[::-1]
+
+
+def build_shelf_plan(model, features=None, image=None):
+    """SSDShelf (ssds/shelf.py): 1x1 transforms (bias), decoder0 / encoder0 / decoder1 in the reference's orders and
+    reversals, the string transforms ("Conv:S") on the last decoder's smallest map, and per level the two ``Head``s
+    (ConvBNReLU + bare 3x3, sigmoid fused on conf) -> finalized ConvPlan (inputs as in ``build_fpn_plan``).  Everything runs
+    in line on the caller's stream."""
+    plan, vals = _neck_inputs(model, features, image)
+    n = len(vals)
+    for i in range(n - 1):
+        if vals[i][3] != 2 * vals[i + 1][3] - 1 or vals[i][4] != 2 * vals[i + 1][4] - 1:
+            raise PlanUnsupported("Shelf pyramid levels are not 2h - 1 of the next: {} over {}".format(vals[i][3:], vals[i + 1][3:]))
+    xx = []
+    for i in range(n):
+        conv = model.transforms[i]
+        if not isinstance(conv, nn.Conv2d) or conv_kind(conv) != "dense" or conv.out_channels % 8:
+            raise PlanUnsupported("transform conv not covered: {}".format(conv))
+        xx.append(plan.conv(vals[i], ConvPack(conv, None, "none", plan.dtype)))
+    xx = xx[::-1]
+    for pyr in model.shelf_head:
+        xx = _record_shelf_pyramid(plan, pyr, xx)
+    for i in range(n, len(model.transforms)):
+        xx.append(record_chain(plan, xx[-1], model.transforms[i], keep_input=True))
+    if len(xx) != len(model.loc) or len(xx) != len(model.conf):
+        raise PlanUnsupported("{} levels, {} / {} heads".format(len(xx), len(model.loc), len(model.conf)))
+    for i, f in enumerate(xx):
+        for heads, act, tag in ((model.loc, "none", "loc"), (model.conf, "sigmoid", "conf")):
+            mods = list(heads[i].children())
+            if len(mods) != 2 or not isinstance(mods[1], nn.Conv2d) or conv_kind(mods[1]) != "dense":
+                raise PlanUnsupported("head not covered: {}".format(type(heads[i]).__name__))
+            (conv, bn, a), = groups_of(mods[0])
+            mid = plan.conv(f, ConvPack(conv, bn, a, plan.dtype), role="tower")
+            plan.head(mid, ConvPack(mods[1], None, "none", plan.dtype), act=act, tag=tag, lane=0, level=i)
+            plan.release(mid)
     return plan.finalize()

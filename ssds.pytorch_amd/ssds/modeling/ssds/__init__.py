@@ -2,3 +2,4 @@
 from .ssd import SSD
 from .fpn import SSDFPN
 from .bifpn import SSDBiFPN
+from .shelf import SSDShelf
