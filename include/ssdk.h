@@ -915,9 +915,18 @@ size_t ssdk_mbse_desc_bytes(void);
  *   w            the four parity images of the weight (ssdk_convt_desc.w_pack), not a KRSC tensor
  *   bias         fp32 [Cout] or NULL;  residual = the skip tensor [N][2H-1][2W-1][Cout] or NULL
  *   N, Cin, H, W, Cout, act, dtype as in ssdk_convt_desc;  k = 3, stride = 2, groups = 1 (anything else: SSDK_E_BADARG)
- * scale, y2, w_frag must be NULL and res_mode 0. */
+ * scale, y2, w_frag must be NULL and res_mode 0.
+ *
+ * SSDK_OP_CAT / SSDK_OP_SPP (executor op kinds 8 / 9, lane 0 only): the channel concatenation and the SPP block of the YOLO necks,
+ * ssdk_cat2 / ssdk_spp of include/ssdk_cat.h.  Like SSDK_OP_CONVT they bring no member to ssdk_op and are described by `conv`:
+ *   CAT  x = a [N][H][W][C1], residual = b, y [N][H][W][Cout];  Cin = C1, Cout = C1 + C2;  res_mode bit 0 set: b is
+ *        [N][H/2][W/2][C2], nearest x2 (SSDK_FUSE_UP2), else [N][H][W][C2] (SSDK_FUSE_SAME);  k = 1, stride = 1
+ *   SPP  x [N][H][W][C], y [N][H][W][4C];  Cin = C, Cout = 4 C;  k = 5, stride = 1;  residual NULL, res_mode 0
+ * N, H, W, dtype as in the descriptors; in_layout = out_layout = SSDK_LAYOUT_NHWC, groups <= 1, act SSDK_ACT_NONE; w, scale, bias,
+ * y2 and w_frag must be NULL.  Anything else: SSDK_E_BADARG. */
 enum { SSDK_OP_CONV = 0, SSDK_OP_MBCONV = 1, SSDK_OP_FUSE = 2, SSDK_OP_STEM7 = 3, SSDK_OP_POOL = 4, SSDK_OP_XPAIR = 5,
-       SSDK_OP_MBSE = 6 /* lane 0 only */, SSDK_OP_CONVT = 7 /* lane 0 only; described by `conv`, see above */ };
+       SSDK_OP_MBSE = 6 /* lane 0 only */, SSDK_OP_CONVT = 7 /* lane 0 only; described by `conv`, see above */,
+       SSDK_OP_CAT = 8, SSDK_OP_SPP = 9 /* both lane 0 only; described by `conv`, see above */ };
 typedef struct ssdk_op {
   int32_t kind, lane;
   ssdk_conv_desc conv;

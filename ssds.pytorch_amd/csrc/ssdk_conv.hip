@@ -27,6 +27,7 @@
 #include "ssdk_conv_common.h"
 #include "ssdk_ctx.h"
 #include "../../include/ssdk_convt.h"
+#include "../../include/ssdk_cat.h"
 
 namespace ssdk {
 
@@ -1505,6 +1506,39 @@ static int run_convt_op(const ssdk_conv_desc* c, hipStream_t st) {
   return ssdk_convt3x3s2(&d, st);
 }
 
+// SSDK_OP_CAT / SSDK_OP_SPP: the op's ssdk_conv_desc read as a concatenation / an SPP block (include/ssdk.h) -> ssdk_cat2 / ssdk_spp
+static int run_cat_op(const ssdk_conv_desc* c, bool spp, hipStream_t st) {
+  const char* what = spp ? "spp" : "cat";
+  if (c->w || c->scale || c->bias || c->y2 || c->w_frag || c->in_layout != LAYOUT_NHWC || c->out_layout != LAYOUT_NHWC || c->groups > 1 ||
+      c->act != SSDK_ACT_NONE || c->stride != 1 || c->k != (spp ? 5 : 1) || (c->res_mode & ~(spp ? 0 : 1)) || (spp && c->residual)) {
+    set_error("%s op: k=%d stride=%d groups=%d act=%d layouts %d/%d res_mode=%d (k %d, stride 1, no activation, NHWC in and out; w, scale, "
+              "bias, y2 and w_frag NULL%s)", what, c->k, c->stride, c->groups, c->act, c->in_layout, c->out_layout, c->res_mode,
+              spp ? 5 : 1, spp ? "; no residual, res_mode 0" : "; res_mode 0 or 1");
+    return SSDK_E_BADARG;
+  }
+  if (spp) {
+    if (c->Cin < 8 || c->Cout != 4 * (long long)c->Cin) {
+      set_error("spp op: Cin=%d Cout=%d (Cout = 4 Cin)", c->Cin, c->Cout);
+      return SSDK_E_BADARG;
+    }
+    ssdk_spp_desc d;
+    memset(&d, 0, sizeof(d));
+    d.x = c->x, d.y = c->y;
+    d.N = c->N, d.H = c->H, d.W = c->W, d.C = c->Cin, d.dtype = c->dtype;
+    return ssdk_spp(&d, st);
+  }
+  if (c->Cin < 8 || c->Cout <= c->Cin) {
+    set_error("cat op: Cin=%d Cout=%d (Cin = C1, Cout = C1 + C2)", c->Cin, c->Cout);
+    return SSDK_E_BADARG;
+  }
+  ssdk_cat_desc d;
+  memset(&d, 0, sizeof(d));
+  d.a = c->x, d.b = c->residual, d.y = c->y;
+  d.N = c->N, d.H = c->H, d.W = c->W, d.C1 = c->Cin, d.C2 = c->Cout - c->Cin, d.dtype = c->dtype;
+  d.mode = (c->res_mode & 1) ? SSDK_FUSE_UP2 : SSDK_FUSE_SAME;
+  return ssdk_cat2(&d, st);
+}
+
 extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* workspace, size_t workspace_bytes,
                                 void* stream) {
   if (int rc = ssdk::ctx_enter(ctx)) return rc;
@@ -1610,6 +1644,8 @@ extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* 
       else if (ops[i].kind == SSDK_OP_XPAIR) rc = ssdk_xpair(&ops[i].xpair, st);
       else if (ops[i].kind == SSDK_OP_MBSE && ops[i].lane == 0) rc = ssdk_mbse(&ops[i].mbse, st);
       else if (ops[i].kind == SSDK_OP_CONVT && ops[i].lane == 0) rc = run_convt_op(&ops[i].conv, st);
+      else if ((ops[i].kind == SSDK_OP_CAT || ops[i].kind == SSDK_OP_SPP) && ops[i].lane == 0)
+        rc = run_cat_op(&ops[i].conv, ops[i].kind == SSDK_OP_SPP, st);
       else {
         set_error("unknown op kind %d", ops[i].kind);
         rc = SSDK_E_BADARG;

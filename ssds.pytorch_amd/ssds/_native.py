@@ -168,8 +168,8 @@ F32, BF16, F16 = _K["SSDK_F32"], _K["SSDK_BF16"], _K["SSDK_F16"]
 ACT = {n: _K["SSDK_ACT_" + n.upper()] for n in ("none", "relu", "relu6", "silu", "sigmoid")}
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 U8 = _K["SSDK_U8"]  # ssdk_preprocess source only
-OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE, OP_CONVT = (
-    _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE", "CONVT"))
+OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE, OP_CONVT, OP_CAT, OP_SPP = (
+    _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE", "CONVT", "CAT", "SPP"))
 MBSE_DW, MBSE_GATE, MBSE_PROJ = 1, 2, 4  # ssdk_mbse_desc.stages bits (0 = all three); the header has no names for them
 FUSE_SAME, FUSE_UP2, FUSE_POOL2 = _K["SSDK_FUSE_SAME"], _K["SSDK_FUSE_UP2"], _K["SSDK_FUSE_POOL2"]
 NCHW, NHWC = _K["SSDK_LAYOUT_NCHW"], _K["SSDK_LAYOUT_NHWC"]
@@ -192,13 +192,25 @@ CONVT_EXPORTS = tuple(_HT.functions)
 ConvTDesc = _HT.structs["ssdk_convt_desc"]
 ConvTDesc.__doc__ = "ssdk_convt_desc: transposed 3x3 / stride 2 / pad 1 convolution + bias (+ skip), the Shelf decoder step."
 
+# include/ssdk_cat.h: the channel concatenation and the SPP block of the YOLO necks, a header of its own for the same reason
+CAT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_cat.h")
+if not os.path.exists(CAT_HEADER_PATH):
+    raise ImportError("include/ssdk_cat.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_cat2 / ssdk_spp from it".format(
+        CAT_HEADER_PATH))
+with open(CAT_HEADER_PATH) as _f:
+    _HC = parse_header(_f.read(), {"ssdk_cat_desc": "CatDesc", "ssdk_spp_desc": "SppDesc"})
+CAT_EXPORTS = tuple(_HC.functions)
+CatDesc, SppDesc = _HC.structs["ssdk_cat_desc"], _HC.structs["ssdk_spp_desc"]
+CatDesc.__doc__ = "ssdk_cat_desc: y = a || b, or a || nearest_x2(b), along the channels (YOLOv3 / PAN concatenations)."
+SppDesc.__doc__ = "ssdk_spp_desc: y = x || maxpool5(x) || maxpool9(x) || maxpool13(x) (the SPP block of YOLOv4)."
+
 
 def _load():
     lib = ctypes.CDLL(LIB_PATH)
 
     def bind(name):
         fn = getattr(lib, name)
-        fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions[name])
+        fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions.get(name) or _HC.functions[name])
         return fn
 
     # version FIRST: a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from the symbol lookup
@@ -210,7 +222,7 @@ def _load():
     if have < ABI_VERSION:
         raise ImportError("libssdk.so at {} is ABI {} but ssds/_native.py is written for ABI {}: rebuild it "
                           "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, have, ABI_VERSION))
-    for name in EXPORTS + CONVT_EXPORTS:
+    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS:
         try:
             bind(name)
         except AttributeError:
@@ -226,14 +238,17 @@ def _load():
                               .format(LIB_PATH, cls.__name__, want, ctypes.sizeof(cls)))
     if lib.ssdk_abi_check(ABI_VERSION, ctypes.sizeof(Op)) != 0:
         raise ImportError("libssdk.so at {}: {}".format(LIB_PATH, lib.ssdk_last_error().decode()))
-    # ssdk_augment_desc, ssdk_mbse_desc and ssdk_convt_desc (ssdk_convt.h) are not behind ssdk_struct_size (its eight indices are part of ABI 245): the
-    # library reports their sizes itself
+    # ssdk_augment_desc, ssdk_mbse_desc, ssdk_convt_desc (ssdk_convt.h), ssdk_cat_desc and ssdk_spp_desc (ssdk_cat.h) are not behind
+    # ssdk_struct_size (its eight indices are part of ABI 245): the library reports their sizes itself
+    mirrors = dict(_H.structs, **_HT.structs)
+    mirrors.update(_HC.structs)
     for cname, fn in (("ssdk_augment_desc", lib.ssdk_augment_desc_bytes), ("ssdk_mbse_desc", lib.ssdk_mbse_desc_bytes),
-                      ("ssdk_convt_desc", lib.ssdk_convt_desc_bytes)):
-        if int(fn()) != ctypes.sizeof(dict(_H.structs, **_HT.structs)[cname]):
+                      ("ssdk_convt_desc", lib.ssdk_convt_desc_bytes), ("ssdk_cat_desc", lib.ssdk_cat_desc_bytes),
+                      ("ssdk_spp_desc", lib.ssdk_spp_desc_bytes)):
+        if int(fn()) != ctypes.sizeof(mirrors[cname]):
             raise ImportError("libssdk.so at {} has sizeof({}) = {} but ssds/_native.py mirrors it with {} bytes: "
                               "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, cname, int(fn()),
-                                                                                   ctypes.sizeof(dict(_H.structs, **_HT.structs)[cname])))
+                                                                                   ctypes.sizeof(mirrors[cname])))
     return lib
 
 

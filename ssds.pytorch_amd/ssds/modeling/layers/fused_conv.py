@@ -626,6 +626,60 @@ def convt_native(x, pk, skip=None, act="none", y=None):
     return y
 
 
+# ---- channel concatenation and SPP block (csrc/ssdk_cat.hip): the YOLO necks' two operations that are no convolution --------
+def cat_supported(c1, c2, h, w, up2):
+    """The host-side mirror of ssdk_cat2's argument checks -> None, or the reason it refuses."""
+    if c1 < 8 or c2 < 8 or c1 % 8 or c2 % 8:
+        return "channel counts {} + {} are not multiples of 8".format(c1, c2)
+    if up2 and (h % 2 or w % 2):
+        return "an upsampled source needs an even {}x{} output".format(h, w)
+    return None
+
+
+def _channels_last(t):
+    return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+
+
+def cat_native(a, b, up2=False, y=None):
+    """One ``ssdk_cat2`` call on channels_last tensors: ``torch.cat((a, b), 1)``, or with ``up2``
+    ``torch.cat((a, F.interpolate(b, scale_factor=2)), 1)`` for ``b`` at half the size of ``a`` -- the same bits."""
+    N.require_device(a, "cat2")
+    a, b = _channels_last(a), _channels_last(b)
+    n, c1, h, w = (int(v) for v in a.shape)
+    c2 = int(b.shape[1])
+    want = (n, c2, h // 2, w // 2) if up2 else (n, c2, h, w)
+    if tuple(b.shape) != want or b.dtype != a.dtype or (up2 and (h % 2 or w % 2)):
+        raise N.SsdkError("cat2: b is {} {}, expected {} {} next to a {}".format(tuple(b.shape), b.dtype, want, a.dtype, tuple(a.shape)))
+    if y is None:
+        y = torch.empty((n, c1 + c2, h, w), device=a.device, dtype=a.dtype, memory_format=torch.channels_last)
+    d = N.CatDesc()
+    d.a, d.b, d.y = a.data_ptr(), b.data_ptr(), y.data_ptr()
+    d.N, d.H, d.W, d.C1, d.C2, d.mode, d.dtype = n, h, w, c1, c2, N.FUSE_UP2 if up2 else N.FUSE_SAME, N.dtype_code(a)
+    with torch.cuda.device(a.device):
+        rc = N.lib.ssdk_cat2(ctypes.byref(d), N.stream_ptr(a.device))
+    N.check(rc, "cat2")
+    STATS["native_layers"] += 1
+    return y
+
+
+def spp_native(x, y=None):
+    """One ``ssdk_spp`` call on a channels_last tensor: ``torch.cat([x] + [F.max_pool2d(x, k, 1, k // 2) for k in (5, 9, 13)], 1)``
+    -- the same bits."""
+    N.require_device(x, "spp")
+    x = _channels_last(x)
+    n, c, h, w = (int(v) for v in x.shape)
+    if y is None:
+        y = torch.empty((n, 4 * c, h, w), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    d = N.SppDesc()
+    d.x, d.y = x.data_ptr(), y.data_ptr()
+    d.N, d.H, d.W, d.C, d.dtype = n, h, w, c, N.dtype_code(x)
+    with torch.cuda.device(x.device):
+        rc = N.lib.ssdk_spp(ctypes.byref(d), N.stream_ptr(x.device))
+    N.check(rc, "spp")
+    STATS["native_layers"] += 1
+    return y
+
+
 def fill_mb_desc(d, x_ptr, y_ptr, n, h, w, pk, dtype_code):
     d.x, d.y = x_ptr, y_ptr
     d.w_expand, d.scale_expand, d.bias_expand = pk.e.w.data_ptr(), pk.e.scale.data_ptr(), pk.e.bias.data_ptr()
@@ -956,6 +1010,26 @@ class ConvPlan(object):
         self.keep.append(pack)
         return (out, n, pack.cout, ho, wo)
 
+    def cat(self, a, b, up2=False):
+        """Channel concatenation ``a || b`` (``up2``: ``b`` at half the size of ``a``, nearest x2 on the way) as one op
+        (csrc/ssdk_cat.hip): [n, c1, h, w], [n, c2, ...] -> [n, c1 + c2, h, w]."""
+        buf, n, c1, h, w = a
+        bbuf, nb, c2, hb, wb = b
+        assert nb == n and (hb, wb) == ((h // 2, w // 2) if up2 else (h, w)) and not (up2 and (h % 2 or w % 2)), (a[1:], b[1:], up2)
+        assert cat_supported(c1, c2, h, w, up2) is None, cat_supported(c1, c2, h, w, up2)
+        out = self.arena.get(n * (c1 + c2) * h * w * self.es)
+        self.layers.append(dict(kind="cat", x=buf, b=bbuf, n=n, h=h, w=w, c1=c1, c2=c2, up2=bool(up2), y=out))
+        return (out, n, c1 + c2, h, w)
+
+    def spp(self, val):
+        """The SPP block ``x || maxpool5(x) || maxpool9(x) || maxpool13(x)`` as one op (csrc/ssdk_cat.hip):
+        [n, c, h, w] -> [n, 4 c, h, w]."""
+        buf, n, c, h, w = val
+        assert c >= 8 and c % 8 == 0, c
+        out = self.arena.get(n * 4 * c * h * w * self.es)
+        self.layers.append(dict(kind="spp", x=buf, n=n, h=h, w=w, ch=c, y=out))
+        return (out, n, 4 * c, h, w)
+
     def xpair(self, val, p1, p2, lane=0):
         buf, n, c, h, w = val
         assert c == p1.cin, (c, p1.cin)
@@ -1074,6 +1148,20 @@ class ConvPlan(object):
                 c.act = c.act2 = N.ACT["none"]
                 c.split, c.dtype, c.in_layout, c.out_layout = pk.cout, self.dtype_code, N.NHWC, N.NHWC
                 continue
+            if kind in ("cat", "spp"):  # carried by the op's ssdk_conv_desc (include/ssdk.h SSDK_OP_CAT / SSDK_OP_SPP)
+                c = op.conv
+                c.x, c.y = self._ptr(L["x"], self.patches, i, "conv.x"), self.arena.ptr(L["y"])
+                if kind == "cat":
+                    op.kind = N.OP_CAT
+                    c.residual = self._ptr(L["b"], self.patches, i, "conv.residual")
+                    c.Cin, c.Cout, c.k, c.res_mode = L["c1"], L["c1"] + L["c2"], 1, 1 if L["up2"] else 0
+                else:
+                    op.kind = N.OP_SPP
+                    c.Cin, c.Cout, c.k = L["ch"], 4 * L["ch"], 5
+                c.N, c.H, c.W, c.stride, c.groups = L["n"], L["h"], L["w"], 1, 1
+                c.act = c.act2 = N.ACT["none"]
+                c.split, c.dtype, c.in_layout, c.out_layout = c.Cout, self.dtype_code, N.NHWC, N.NHWC
+                continue
             if kind == "xpair":
                 op.kind = N.OP_XPAIR
                 op.lane = L.get("lane", 0)
@@ -1143,6 +1231,17 @@ class ConvPlan(object):
                 byt = es * (sum(v[1] * v[2] * v[3] * v[4] for v in srcs) + n * ch * h * w)
                 rows.append(dict(name="fuse x%d %d @%dx%d" % (len(srcs), ch, h, w), flops=2.0 * len(srcs) * n * ch * h * w,
                                  bytes=float(byt), kind="fuse"))
+                continue
+            if L.get("kind") == "cat":  # data movement: both sources and the output once
+                n, h, w, c1, c2 = L["n"], L["h"], L["w"], L["c1"], L["c2"]
+                src_b = (h // 2) * (w // 2) if L["up2"] else h * w
+                rows.append(dict(name="cat %d+%d%s @%dx%d" % (c1, c2, " up2" if L["up2"] else "", h, w), flops=0.0,
+                                 bytes=float(es * n * (h * w * c1 + src_b * c2 + h * w * (c1 + c2))), kind="fuse"))
+                continue
+            if L.get("kind") == "spp":  # comparisons only: x once, the four slices once
+                n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
+                rows.append(dict(name="spp %d k5,9,13 @%dx%d" % (ch, h, w), flops=0.0, bytes=float(es * n * h * w * 5 * ch),
+                                 kind="fuse"))
                 continue
             pk, n, h, w = L["pack"], L["n"], L["h"], L["w"]
             if L.get("kind") == "mbse":  # depthwise + SE + gated projection: x in, y out, t written and read once, the weights

@@ -3,15 +3,16 @@ group becomes one descriptor of the fused HIP kernels, block-level residual adds
 the projecting 1x1 conv, and the loc | conf convs of each level become one split-output GEMM.
 
 Covered: MobileNet v1/v2 backbones (nets/mobilenet.py), the SSD extras and heads (ssds/ssd.py) -- i.e. the
-network of BASELINE configs 1, 2 and 4 -- and the FPN / BiFPN / Shelf necks with their towers or heads (ssds/fpn.py,
-ssds/bifpn.py, ssds/shelf.py; configs 3 and 5) on top of backbone feature maps handed in as external inputs.  Anything else
+network of BASELINE configs 1, 2 and 4 -- and the FPN / BiFPN / Shelf / YOLOv3 / YOLOv4 necks with their towers or heads
+(ssds/fpn.py, ssds/bifpn.py, ssds/shelf.py, ssds/yolo.py; configs 3 and 5) on top of backbone feature maps handed in as external inputs.  Anything else
 raises ``PlanUnsupported`` and the caller runs the module-by-module path instead (and says so in
 ``fused_conv.STATS``)."""
 import torch.nn as nn
 
 import os
 
-from .fused_conv import ConvPack, ConvPlan, ConvTPack, MbPack, MbSePack, StemPack, conv_kind, pack_heads, sequential_groups, xpair_supported
+from .fused_conv import (ConvPack, ConvPlan, ConvTPack, MbPack, MbSePack, StemPack, cat_supported, conv_kind, pack_heads, sequential_groups,
+                         xpair_supported)
 
 
 class PlanUnsupported(Exception):
@@ -532,4 +533,132 @@ def build_shelf_plan(model, features=None, image=None):
             mid = plan.conv(f, ConvPack(conv, bn, a, plan.dtype), role="tower")
             plan.head(mid, ConvPack(mods[1], None, "none", plan.dtype), act=act, tag=tag, lane=0, level=i)
             plan.release(mid)
+    return plan.finalize()
+
+
+# --------------------------------------------------------------------------------------------------------------
+# YOLOv3 / YOLOv4 necks + per-level heads (ssds/yolo.py)
+# --------------------------------------------------------------------------------------------------------------
+def _record_cat(plan, a, b, up2):
+    """``a || b`` (``up2``: ``b`` is the coarser level, nearest x2 on the way) as one ssdk_cat2 op; PlanUnsupported with the
+    reason for maps that are not exact halves and for channel counts the kernel does not take."""
+    if up2 and (b[3] * 2 != a[3] or b[4] * 2 != a[4]):
+        raise PlanUnsupported("YOLO levels are not exact halves: {} over {}".format(a[3:], b[3:]))
+    if not up2 and tuple(a[3:]) != tuple(b[3:]):
+        raise PlanUnsupported("concatenation of maps of different sizes: {} and {}".format(a[3:], b[3:]))
+    why = cat_supported(a[2], b[2], a[3], a[4], up2)
+    if why:
+        raise PlanUnsupported("concatenation not covered by ssdk_cat2: " + why)
+    return plan.cat(a, b, up2=up2)
+
+
+def _record_heads(plan, model, levels):
+    """Per level the two ``Head``s (ConvBNReLU + bare 3x3, sigmoid fused on conf), in line, as in ``build_shelf_plan``."""
+    if len(levels) != len(model.loc) or len(levels) != len(model.conf):
+        raise PlanUnsupported("{} levels, {} / {} heads".format(len(levels), len(model.loc), len(model.conf)))
+    for i, f in enumerate(levels):
+        for heads, act, tag in ((model.loc, "none", "loc"), (model.conf, "sigmoid", "conf")):
+            mods = list(heads[i].children())
+            if len(mods) != 2 or not isinstance(mods[1], nn.Conv2d) or conv_kind(mods[1]) != "dense":
+                raise PlanUnsupported("head not covered: {}".format(type(heads[i]).__name__))
+            (conv, bn, a), = groups_of(mods[0])
+            mid = plan.conv(f, ConvPack(conv, bn, a, plan.dtype), role="tower")
+            plan.head(mid, ConvPack(mods[1], None, "none", plan.dtype), act=act, tag=tag, lane=0, level=i)
+            plan.release(mid)
+
+
+def build_yolov3_plan(model, features=None, image=None):
+    """YOLOV3 (ssds/yolo.py): from the smallest backbone map up, ``extras[i]`` on the concatenation of backbone map i with the
+    nearest-x2 upsample of ``transforms[i]`` of the level below (one ssdk_cat2 op: the upsampled tensor is never written); the
+    first string extra on the RAW last backbone map, later ones on the previous extra; per level the two heads -> finalized
+    ConvPlan (inputs as in ``build_fpn_plan``).  Everything runs in line on the caller's stream."""
+    plan, vals = _neck_inputs(model, features, image)
+    n = len(vals)
+    if len(model.transforms) != n - 1 or len(model.extras) < n:
+        raise PlanUnsupported("{} backbone maps, {} transforms, {} extras".format(n, len(model.transforms), len(model.extras)))
+    levels = [None] * n
+    xx = None
+    for i in range(n - 1, -1, -1):
+        if i == n - 1:
+            xx = record_chain(plan, vals[i], model.extras[i], keep_input=True)  # (the raw map is read again by the first string extra)
+        else:
+            up = record_chain(plan, xx, model.transforms[i], keep_input=True)  # (xx is level i + 1: its heads come later)
+            fused = _record_cat(plan, vals[i], up, True)
+            plan.release(up)
+            plan.release(vals[i])
+            xx = record_chain(plan, fused, model.extras[i])
+        levels[i] = xx
+    for i in range(n, len(model.extras)):
+        xx = record_chain(plan, vals[n - 1] if i == n else xx, model.extras[i], keep_input=True)
+        levels.append(xx)
+    plan.release(vals[n - 1])
+    _record_heads(plan, model, levels)
+    return plan.finalize()
+
+
+def _record_pan(plan, m, xx):
+    """PANModule (ssds/yolo.py) on the values ``xx``, largest map first: top-down ``cat(x[i-1], up2(conv3x3(x[i])))`` +
+    ConvBNReLUx2, then bottom-up ``cat(x[i+1], conv3x3/s2(x[i]))`` + ConvBNReLUx2.  A level's old value goes back to the arena
+    when its last reader -- the concatenation that replaces it, or the step that reads it for its neighbour -- is recorded."""
+    from ssds.modeling.ssds.yolo import PANModule
+
+    if not isinstance(m, PANModule) or m.levels != len(xx):
+        raise PlanUnsupported("neck block {} has no planner".format(type(m).__name__))
+    xx = list(xx)
+    n = m.levels
+    for i in range(n - 1, 0, -1):
+        up = record_chain(plan, xx[i], getattr(m, "top-down-{}-to-{}".format(i, i - 1)), keep_input=True)  # (read again bottom-up)
+        fused = _record_cat(plan, xx[i - 1], up, True)
+        plan.release(up)
+        plan.release(xx[i - 1])
+        xx[i - 1] = record_chain(plan, fused, getattr(m, "top-down-{}".format(i - 1)))
+    for i in range(0, n - 1):
+        down = record_chain(plan, xx[i], getattr(m, "bottom-up-{}-to-{}".format(i, i + 1)), keep_input=True)  # (xx[i] is an output)
+        fused = _record_cat(plan, xx[i + 1], down, False)
+        plan.release(down)
+        plan.release(xx[i + 1])
+        xx[i + 1] = record_chain(plan, fused, getattr(m, "bottom-up-{}".format(i + 1)))
+    return xx
+
+
+def _record_spp_transform(plan, val, seq):
+    """``Sequential(ConvBNReLU, SPPModule(3), ConvBNReLU)`` of YOLOv4's last transform: the SPP block is one ssdk_spp op."""
+    from ssds.modeling.ssds.yolo import SPPModule
+
+    mods = list(seq.children())
+    if len(mods) != 3 or not isinstance(mods[1], SPPModule):
+        raise PlanUnsupported("transform not covered: {}".format(type(seq).__name__))
+    spp = mods[1]
+    if spp.pool_type != "max_pool":
+        raise PlanUnsupported("SPP with {} has no kernel (ssdk_spp is the max-pool block)".format(spp.pool_type))
+    if spp.num_levels != 3:
+        raise PlanUnsupported("SPP with {} levels has no kernel (ssdk_spp pools 5, 9 and 13)".format(spp.num_levels))
+    mid = record_chain(plan, val, mods[0])
+    if mid[2] % 8:
+        raise PlanUnsupported("SPP on {} channels is not covered by ssdk_spp (multiples of 8)".format(mid[2]))
+    pooled = plan.spp(mid)
+    plan.release(mid)
+    return record_chain(plan, pooled, mods[2])
+
+
+def build_yolov4_plan(model, features=None, image=None):
+    """YOLOV4 (ssds/yolo.py): the 3x3 ``transforms`` (the last one through the SPP block), the stacked PAN modules, the string
+    extras behind the last level and per level the two heads -> finalized ConvPlan (inputs as in ``build_fpn_plan``)."""
+    from ssds.modeling.ssds.yolo import SPPModule
+
+    plan, vals = _neck_inputs(model, features, image)
+    n = len(vals)
+    if len(model.transforms) != n:
+        raise PlanUnsupported("{} backbone maps, {} transforms".format(n, len(model.transforms)))
+    xx = []
+    for i, t in enumerate(model.transforms):
+        if any(isinstance(m, SPPModule) for m in t.modules()):
+            xx.append(_record_spp_transform(plan, vals[i], t))
+        else:
+            xx.append(record_chain(plan, vals[i], t))
+    for m in model.fpn:
+        xx = _record_pan(plan, m, xx)
+    for e in model.extras:
+        xx.append(record_chain(plan, xx[-1], e, keep_input=True))
+    _record_heads(plan, model, xx)
     return plan.finalize()

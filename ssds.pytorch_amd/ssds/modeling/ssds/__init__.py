@@ -3,3 +3,4 @@ from .ssd import SSD
 from .fpn import SSDFPN
 from .bifpn import SSDBiFPN
 from .shelf import SSDShelf
+from .yolo import YOLOV3, YOLOV4
