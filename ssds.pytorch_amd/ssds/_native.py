@@ -204,13 +204,24 @@ CatDesc, SppDesc = _HC.structs["ssdk_cat_desc"], _HC.structs["ssdk_spp_desc"]
 CatDesc.__doc__ = "ssdk_cat_desc: y = a || b, or a || nearest_x2(b), along the channels (YOLOv3 / PAN concatenations)."
 SppDesc.__doc__ = "ssdk_spp_desc: y = x || maxpool5(x) || maxpool9(x) || maxpool13(x) (the SPP block of YOLOv4)."
 
+# include/ssdk_cattrain.h: the same two operations of the YOLO TRAINING step, forward and backward on NCHW tensors (no descriptors)
+CATTRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_cattrain.h")
+if not os.path.exists(CATTRAIN_HEADER_PATH):
+    raise ImportError("include/ssdk_cattrain.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_cat_train_* / "
+                      "ssdk_spp_train_* from it".format(CATTRAIN_HEADER_PATH))
+with open(CATTRAIN_HEADER_PATH) as _f:
+    _HCT = parse_header(_f.read())
+CATTRAIN_EXPORTS = tuple(_HCT.functions)
+SPP_TRAIN_MAX_SIDE = _HCT.constants["SSDK_SPP_TRAIN_MAX_SIDE"]  # the largest H / W ssdk_spp_train_* stage in LDS
+
 
 def _load():
     lib = ctypes.CDLL(LIB_PATH)
 
     def bind(name):
         fn = getattr(lib, name)
-        fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions.get(name) or _HC.functions[name])
+        fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions.get(name) or _HC.functions.get(name)
+                                   or _HCT.functions[name])
         return fn
 
     # version FIRST: a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from the symbol lookup
@@ -222,11 +233,12 @@ def _load():
     if have < ABI_VERSION:
         raise ImportError("libssdk.so at {} is ABI {} but ssds/_native.py is written for ABI {}: rebuild it "
                           "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, have, ABI_VERSION))
-    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS:
+    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS + CATTRAIN_EXPORTS:
         try:
             bind(name)
         except AttributeError:
-            raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h declares: rebuild it "
+            raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h (or ssdk_convt.h, ssdk_cat.h, "
+                              "ssdk_cattrain.h next to it) declares: rebuild it "
                               "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, name))
     # the ctypes mirrors must have the layout the library was BUILT with: a shorter struct would be read past its end.
     # SSDK_SIZEOF_X is the index of struct ssdk_x

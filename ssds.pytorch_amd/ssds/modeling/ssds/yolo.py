@@ -12,8 +12,10 @@ on maps that are exact halves of each other; anything else fails in ``torch.cat`
 MI355X execution (eval, 16-bit, HIP device): backbone, neck and heads are one recorded plan (layers/planner.py
 ``build_yolov3_plan`` / ``build_yolov4_plan``).  The two operations the plan had no op for are one launch each of
 csrc/ssdk_cat.hip: ``ssdk_cat2`` writes ``a || nearest_x2(b)`` without ever storing the upsampled tensor, ``ssdk_spp`` computes
-the three pools from one staging of ``x``.  Training is the module path: torch's ``cat`` / ``interpolate`` / ``max_pool2d``
-autograd around the convolution layers that tools/train_ddp.py swaps for kernel-backed ones."""
+the three pools from one staging of ``x``.  Training is the module path around the convolution layers that
+ssds/utils/train_ddp.py swaps for kernel-backed ones; with the ``native_cat`` flag (layers/cattrain.py ``use_native_cat``) the
+concatenations and the SPP block run forward and backward on csrc/ssdk_cattrain.hip, and without it -- or for operands the kernels
+do not take -- on torch's ``cat`` / ``interpolate`` / ``max_pool2d`` autograd."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -33,11 +35,24 @@ def _count_fallback(f0, training):
             FC.STATS["torch_fallback_layers"] += 1
 
 
+def _cat(native, a, b, up):
+    """cat((a, nearest_x2(b) if up else b), 1): on csrc/ssdk_cattrain.hip when ``native`` and the operands meet its contract."""
+    if native:
+        from ssds.modeling.layers import cattrain
+
+        y = cattrain.try_cat2(a, b, cattrain.UP2 if up else cattrain.SAME)
+        if y is not None:
+            return y
+    return torch.cat((a, F.interpolate(b, scale_factor=2, mode="nearest") if up else b), dim=1)
+
+
 def _refuse(layer):
     raise ValueError("{} does not support by YOLO".format(layer))
 
 
 class YOLOV3(NeckPlanMixin, SSDSBase):
+    native_cat = False  # layers/cattrain.py use_native_cat: the concatenations of the training step on csrc/ssdk_cattrain.hip
+
     def __init__(self, backbone, extras, head, num_classes):
         super(YOLOV3, self).__init__(backbone, num_classes)
         self.transforms = nn.ModuleList(extras[0])
@@ -73,7 +88,7 @@ class YOLOV3(NeckPlanMixin, SSDSBase):
         raw_last = xx = features[-1]
         for i in range(n - 1, -1, -1):
             if i != n - 1:
-                xx = torch.cat((features[i], F.interpolate(self.transforms[i](xx), scale_factor=2)), dim=1)
+                xx = _cat(self.native_cat, features[i], self.transforms[i](xx), True)
             xx = self.extras[i](xx)
             features[i] = xx
         # the first string extra reads the RAW last backbone map, later ones the previous extra (reference yolo.py:75-81)
@@ -123,12 +138,20 @@ class SPPModule(nn.Module):
     """cat(x, pool_5(x), pool_9(x), ... ) over ``num_levels`` stride-1 pools of windows 4 i + 5 with padding k // 2 (reference
     yolo.py:161-184); ``pool_type`` "max_pool" or anything else for average pooling.  No parameters."""
 
+    native_cat = False  # layers/cattrain.py use_native_cat (three max-pool levels only)
+
     def __init__(self, num_levels, pool_type="max_pool"):
         super(SPPModule, self).__init__()
         self.num_levels = num_levels
         self.pool_type = pool_type
 
     def forward(self, x):
+        if self.native_cat and self.num_levels == 3 and self.pool_type == "max_pool":
+            from ssds.modeling.layers import cattrain
+
+            y = cattrain.try_spp(x)
+            if y is not None:
+                return y
         pool = F.max_pool2d if self.pool_type == "max_pool" else F.avg_pool2d
         out = [x]
         for i in range(self.num_levels):
@@ -140,6 +163,8 @@ class SPPModule(nn.Module):
 class PANModule(nn.Module):
     """One path-aggregation block over ``len(channels)`` levels, largest map first (reference yolo.py:187-247): top-down
     ``cat(x[i-1], up2(conv3x3(x[i])))`` + ``ConvBNReLUx2``, then bottom-up ``cat(x[i+1], conv3x3/s2(x[i]))`` + ``ConvBNReLUx2``."""
+
+    native_cat = False  # layers/cattrain.py use_native_cat
 
     def __init__(self, channels):
         super(PANModule, self).__init__()
@@ -160,11 +185,11 @@ class PANModule(nn.Module):
         assert len(xx) == self.levels
         xx = list(xx)
         for i in range(self.levels - 1, 0, -1):
-            up = F.interpolate(getattr(self, "top-down-{}-to-{}".format(i, i - 1))(xx[i]), scale_factor=2, mode="nearest")
-            xx[i - 1] = getattr(self, "top-down-{}".format(i - 1))(torch.cat((xx[i - 1], up), dim=1))
+            up = getattr(self, "top-down-{}-to-{}".format(i, i - 1))(xx[i])
+            xx[i - 1] = getattr(self, "top-down-{}".format(i - 1))(_cat(self.native_cat, xx[i - 1], up, True))
         for i in range(0, self.levels - 1):
             down = getattr(self, "bottom-up-{}-to-{}".format(i, i + 1))(xx[i])
-            xx[i + 1] = getattr(self, "bottom-up-{}".format(i + 1))(torch.cat((xx[i + 1], down), dim=1))
+            xx[i + 1] = getattr(self, "bottom-up-{}".format(i + 1))(_cat(self.native_cat, xx[i + 1], down, False))
         return xx
 
 

@@ -103,7 +103,9 @@ class Solver(object):
         from ssds.modeling.layers import denseconv
         from ssds.modeling.ssds.bifpn import SSDBiFPN
         from ssds.modeling.ssds.fpn import SSDFPN
+        from ssds.modeling.ssds.yolo import YOLOV3, YOLOV4
 
+        yolo = isinstance(self.model, (YOLOV3, YOLOV4))
         if isinstance(self.model, (SSDFPN, SSDBiFPN)) and denseconv.enabled():
             # dense 3x3 of the FPN / BiFPN detectors (towers, smoothing, heads, ResNet bottlenecks, extras): forward, input gradient,
             # weight gradient on csrc/ssdk_conv3train.hip.  Before the im2col swap below, which then skips the extras of these
@@ -115,6 +117,20 @@ class Solver(object):
             # the BiFPN weighted fusions, the FPN top-down upsample-adds and the ResNet stem's max-pool: forward and backward on
             # csrc/ssdk_necktrain.hip.  SSDK_NECK_TRAIN=0: the eager expressions / nn.MaxPool2d.  SSD models are not touched.
             neckfuse.use_native_neck(self.model)
+        if yolo:
+            # YOLOv3 / YOLOv4, each part under its own switch.  SSDK_DENSE3_TRAIN: every 3x3 of both shipped configs
+            # (transforms, ConvBNReLUx2, heads, PAN stride-2 layers, ResNet BasicBlocks) fits csrc/ssdk_conv3train.hip -- before the
+            # im2col swap below, which then skips the extras; measured slower than nn.Conv2d on these models, so here an unset
+            # variable means 0 (denseconv.YOLO_DEFAULT).  SSDK_NECK_TRAIN: the ResNet stem max-pool on csrc/ssdk_necktrain.hip (all
+            # use_native_neck touches on these models).  SSDK_CAT_TRAIN: the concatenations and the SPP block on csrc/ssdk_cattrain.hip.
+            from ssds.modeling.layers import cattrain
+
+            if denseconv.enabled(denseconv.YOLO_DEFAULT):
+                denseconv.use_native_dense3x3(self.model)
+            if neckfuse.enabled():
+                neckfuse.use_native_neck(self.model)
+            if cattrain.enabled():
+                cattrain.use_native_cat(self.model)
         conv3 = os.environ.get("SSDK_CONV3_NATIVE", "2")
         from ssds.modeling.layers import headconv
 
