@@ -12,7 +12,10 @@ padding, so an ``h x w`` map becomes ``(2h - 1) x (2w - 1)``: the model only run
 MI355X execution (eval, 16-bit, HIP device): the whole neck and the heads are one recorded plan
 (layers/planner.py ``build_shelf_plan``) -- the transposed convolution + bias + skip add is ONE launch of
 csrc/ssdk_convt.hip, each ``SharedBlock`` two fused 3x3 launches from the same weight (BatchNorm 1 + ReLU; BatchNorm 2 +
-skip + ReLU).  Training keeps the module path: ``ConvTranspose2d`` and ``Dropout2d`` run on PyTorch-ROCm."""
+skip + ReLU).  Training (utils/train_ddp.Solver): under ``SSDK_CONVT_TRAIN=1`` the transposed convolution + bias + skip add, its input
+gradient and its weight + bias gradient run on csrc/ssdk_convttrain.hip (layers/convttrain.py ``ShelfConvT``, an in-place class swap);
+the switch is off by default, because the step measured slower with it, and ``nn.ConvTranspose2d`` then runs on
+PyTorch-ROCm.  ``Dropout2d`` stays torch's either way (one broadcast multiply by an [N, C, 1, 1] mask, drawn from torch's generator)."""
 from collections import OrderedDict
 
 import torch
@@ -62,7 +65,11 @@ class ShelfPyramid(nn.Module):
         out, x = [], xx[0]
         for i in range(len(xx)):
             if i > 0:
-                x = getattr(self, "conv{}".format(i))(x) + xx[i]
+                conv = getattr(self, "conv{}".format(i))
+                if getattr(conv, "takes_skip", False):  # layers/convttrain.ShelfConvT: the add rides on the forward kernel
+                    x = conv(x, skip=xx[i])
+                else:
+                    x = conv(x) + xx[i]
             x = getattr(self, "block{}".format(i))(x)
             out.append(x)
         return out[::-1]

@@ -131,6 +131,24 @@ class Solver(object):
                 neckfuse.use_native_neck(self.model)
             if cattrain.enabled():
                 cattrain.use_native_cat(self.model)
+        from ssds.modeling.ssds.shelf import SSDShelf
+
+        if isinstance(self.model, SSDShelf):
+            # SSDShelf, each part under its own switch.  SSDK_CONVT_TRAIN: the decoders' transposed 3x3 / stride 2 +
+            # bias + skip add, forward and gradients on csrc/ssdk_convttrain.hip; the step measured slower with it (50.34 against
+            # 47.36 ms at batch 32), so an unset variable means 0 (convttrain.DEFAULT).  SSDK_DENSE3_TRAIN: the SharedBlock 3x3 (one weight
+            # on two maps), the encoder's stride-2 layers, the heads and the ResNet blocks fit csrc/ssdk_conv3train.hip -- before the
+            # im2col swap below; those kernels measured slower than nn.Conv2d on ResNet-18 models and were never timed on Shelf, so
+            # here an unset variable means 0, as on YOLO (denseconv.YOLO_DEFAULT).  SSDK_NECK_TRAIN: the ResNet stem max-pool on
+            # csrc/ssdk_necktrain.hip (all use_native_neck touches on this model).
+            from ssds.modeling.layers import convttrain
+
+            if convttrain.enabled():
+                convttrain.use_native_convt(self.model)
+            if denseconv.enabled(denseconv.YOLO_DEFAULT):
+                denseconv.use_native_dense3x3(self.model)
+            if neckfuse.enabled():
+                neckfuse.use_native_neck(self.model)
         conv3 = os.environ.get("SSDK_CONV3_NATIVE", "2")
         from ssds.modeling.layers import headconv
 

@@ -36,8 +36,8 @@ ap.add_argument("--sync-bn", type=int, default=0, choices=(0, 1),
 ap.add_argument("--optimizer", default="sgd", choices=("sgd", "adam", "amsgrad", "rmsprop"),
                 help="the config's optimizer (core/optimizer.configure_optimizer: the ssdk kernels on a HIP device)")
 ap.add_argument("--cfg", default="ssd_mobilenetv2_512.yml",
-                help="a config under experiments/cfgs (bifpn_regnetx016_896.yml, fpn_resnext50_640.yml: the grouped backbones; give a "
-                     "--batch that fits)")
+                help="a config under experiments/cfgs (bifpn_regnetx016_896.yml, fpn_resnext50_640.yml: the grouped backbones; "
+                     "shelf_resnet18_513.yml: the Shelf step, --batch 32; give a --batch that fits)")
 ap.add_argument("--size", type=int, default=0, help="square input size instead of the config's (300: planes that are not a multiple of 8)")
 ap.add_argument("--cpu", type=int, default=0,
                 help="(tests/test_ddp_cpu.py) 1: ONLY the launcher / rank / barrier / MAX-time / rank-0-print logic of this "
@@ -150,12 +150,15 @@ if rank == 0:
     from ssds.modeling.layers import cattrain as _CT
 
     _cat = _CT.STATS["cat_forward"] + _CT.STATS["spp_forward"] > 0  # SSDK_CAT_TRAIN: the concatenations / SPP block of a YOLO model ran natively
+    from ssds.modeling.layers import convttrain as _CV
+
+    _convt = _CV.STATS["native_forward"] > 0  # SSDK_CONVT_TRAIN: the transposed convolutions of a Shelf model ran natively
     _name = "SSD-MobileNetV2" if args.cfg == "ssd_mobilenetv2_512.yml" else "%s-%s" % (cfg.MODEL.SSDS, cfg.MODEL.NETS)
     print(json.dumps({"metric": "images/sec (DDP training step) %s@%d" % (_name, cfg.MODEL.IMAGE_SIZE[0]), "value": round(world * args.batch * args.steps / el, 1),
                       "n_gpus": world, "ms_per_step": round(el / args.steps * 1e3, 2), "batch_per_gpu": args.batch,
                       "cls_loss": float(c), "loc_loss": float(l), "dtype": "bf16 autocast", "hipgraph": bool(args.graph), "sync_bn": bool(args.sync_bn),
                       "optimizer": args.optimizer, "cfg": args.cfg, "gconv_train": os.environ.get("SSDK_GCONV_TRAIN", "1") != "0",
-                      "dense3_train": _dense3, "neck_train": _neck, "stem7_train": _stem7, "mbconv_train": _mbconv, "cat_train": _cat,
+                      "dense3_train": _dense3, "neck_train": _neck, "stem7_train": _stem7, "mbconv_train": _mbconv, "cat_train": _cat, "convt_train": _convt,
                       "peak_allocated_MiB": None if args.cpu else round(torch.cuda.max_memory_allocated() / 2 ** 20, 1),
                       "data": "synthetic" if not args.cpu else "stub (CPU / gloo run of the rank logic)"}))
 if world > 1:
