@@ -201,8 +201,22 @@ class StemPack(object):
         self.cin, self.cout, self.act = 3, conv.out_channels, act
 
 
-def stem7_native(x, pack):
-    """[N,3,H,W] image (NCHW contiguous or channels_last) -> channels_last [N,Cout,H/2,W/2]."""
+def _out_tensor(y, shape, like, memory_format, what):
+    """The output of a ``*_native`` call: a fresh ``torch.empty`` (``y`` None), or the caller's own buffer once it is what the
+    call would have allocated -- shape, dtype, device and memory format -- since the kernel is handed its bare address."""
+    shape = tuple(int(v) for v in shape)
+    if y is None:
+        return torch.empty(shape, device=like.device, dtype=like.dtype, memory_format=memory_format)
+    if (tuple(y.shape) != shape or y.dtype != like.dtype or y.device != like.device
+            or not y.is_contiguous(memory_format=memory_format)):
+        raise N.SsdkError("{}: the output handed in is {} {} on {} with strides {}, expected {} {} on {} in {}".format(
+            what, tuple(y.shape), y.dtype, y.device, tuple(y.stride()), shape, like.dtype, like.device,
+            "channels_last" if memory_format == torch.channels_last else "contiguous"))
+    return y
+
+
+def stem7_native(x, pack, y=None):
+    """[N,3,H,W] image (NCHW contiguous or channels_last) -> channels_last [N,Cout,H/2,W/2] (``y``: write there)."""
     N.require_device(x, "conv_stem7")
     n, c, h, w = (int(v) for v in x.shape)
     layout = N.NCHW
@@ -210,7 +224,7 @@ def stem7_native(x, pack):
         x = x.contiguous(memory_format=torch.channels_last)
         layout = N.NHWC
     ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
-    y = torch.empty((n, pack.cout, ho, wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    y = _out_tensor(y, (n, pack.cout, ho, wo), x, torch.channels_last, "conv_stem7")
     d = N.StemDesc()
     d.x, d.w, d.scale, d.bias, d.y = x.data_ptr(), pack.w.data_ptr(), pack.scale.data_ptr(), pack.bias.data_ptr(), y.data_ptr()
     d.N, d.H, d.W, d.Cin, d.Cout, d.act, d.dtype, d.in_layout = n, h, w, c, pack.cout, N.ACT[pack.act], N.dtype_code(x), layout
@@ -220,14 +234,14 @@ def stem7_native(x, pack):
     return y
 
 
-def maxpool_native(x):
-    """F.max_pool2d(x, 3, 2, 1) on a channels_last tensor."""
+def maxpool_native(x, y=None):
+    """F.max_pool2d(x, 3, 2, 1) on a channels_last tensor (``y``: write there)."""
     N.require_device(x, "maxpool3x3s2")
     if not x.is_contiguous(memory_format=torch.channels_last):
         x = x.contiguous(memory_format=torch.channels_last)
     n, c, h, w = (int(v) for v in x.shape)
     ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-    y = torch.empty((n, c, ho, wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    y = _out_tensor(y, (n, c, ho, wo), x, torch.channels_last, "maxpool3x3s2")
     d = N.PoolDesc()
     d.x, d.y = x.data_ptr(), y.data_ptr()
     d.N, d.H, d.W, d.C, d.dtype = n, h, w, c, N.dtype_code(x)
@@ -719,14 +733,15 @@ def fill_xpair_desc(d, x_ptr, y_ptr, n, h, w, p1, p2, dtype_code):
     return d
 
 
-def xpair_native(x, p1, p2):
-    """Conv 1x1 + BN + act -> Conv 3x3 / stride 2 + BN + act on a small map in one launch; x channels_last."""
+def xpair_native(x, p1, p2, y=None):
+    """Conv 1x1 + BN + act -> Conv 3x3 / stride 2 + BN + act on a small map in one launch; x channels_last (``y``: write
+    there)."""
     N.require_device(x, "xpair")
     if not x.is_contiguous(memory_format=torch.channels_last):
         x = x.contiguous(memory_format=torch.channels_last)
     n, c, h, w = (int(v) for v in x.shape)
     ho, wo = _out_hw(h, w, 3, 2)
-    y = torch.empty((n, p2.cout, ho, wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    y = _out_tensor(y, (n, p2.cout, ho, wo), x, torch.channels_last, "xpair")
     d = fill_xpair_desc(N.XpairDesc(), x.data_ptr(), y.data_ptr(), n, h, w, p1, p2, N.dtype_code(x))
     with torch.cuda.device(x.device):
         rc = N.lib.ssdk_xpair(ctypes.byref(d), N.stream_ptr(x.device))
@@ -735,14 +750,15 @@ def xpair_native(x, p1, p2):
     return y
 
 
-def fuse_native(a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_c=N.FUSE_SAME):
-    """y = w0*a + w1*R_b(b) [+ w2*R_c(c)] (BiFPN weighted fusion, csrc/ssdk_fuse.hip); channels_last tensors."""
+def fuse_native(a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_c=N.FUSE_SAME, y=None):
+    """y = w0*a + w1*R_b(b) [+ w2*R_c(c)] (BiFPN weighted fusion, csrc/ssdk_fuse.hip); channels_last tensors (``y``: write
+    there)."""
     N.require_device(a, "fuse")
     ts = [t if t is None or t.is_contiguous(memory_format=torch.channels_last) else
           t.contiguous(memory_format=torch.channels_last) for t in (a, b, c)]
     a, b, c = ts
     n, ch, h, w = (int(v) for v in a.shape)
-    y = torch.empty_like(a, memory_format=torch.channels_last)
+    y = _out_tensor(y, (n, ch, h, w), a, torch.channels_last, "fuse")
     d = N.FuseDesc()
     d.a, d.b, d.c, d.y = a.data_ptr(), b.data_ptr(), (c.data_ptr() if c is not None else None), y.data_ptr()
     d.w0, d.w1, d.w2 = (float(v) for v in weights)
@@ -758,8 +774,8 @@ def fuse_native(a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_
     return y
 
 
-def mbconv_native(x, pk, variant=0):
-    """One fused inverted-residual block; x channels_last [N,Cin,H,W] -> channels_last [N,Cout,Ho,Wo].
+def mbconv_native(x, pk, variant=0, y=None):
+    """One fused inverted-residual block; x channels_last [N,Cin,H,W] -> channels_last [N,Cout,Ho,Wo] (``y``: write there).
     ``variant``: 0 automatic, 1 register-flow kernel wherever it exists, -1 LDS-tiled kernel only (ssdk_mbconv_desc)."""
     N.require_device(x, "mbconv")
     stem = pk.stem
@@ -772,7 +788,7 @@ def mbconv_native(x, pk, variant=0):
     n, c, h, w = (int(v) for v in x.shape)
     hs, ws = _out_hw(h, w, 3, 2) if pk.stem else (h, w)
     ho, wo = _out_hw(hs, ws, 3, pk.stride)
-    y = torch.empty((n, pk.cout, ho, wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    y = _out_tensor(y, (n, pk.cout, ho, wo), x, torch.channels_last, "mbconv")
     d = fill_mb_desc(N.MbConvDesc(), x.data_ptr(), y.data_ptr(), n, h, w, pk, N.dtype_code(x))
     d.stem = stem
     d.variant = int(variant)
@@ -825,9 +841,10 @@ def fill_desc(d, x_ptr, n, h, w, pack, dtype_code, act, y_ptr, in_layout=N.NHWC,
     return d
 
 
-def conv_native(x, pack, act=None, residual=None, nchw_out=False, split=None, act2=None, res_mode=0):
+def conv_native(x, pack, act=None, residual=None, nchw_out=False, split=None, act2=None, res_mode=0, y=None, y2=None):
     """One fused layer.  x: [N,C,H,W] tensor in channels_last memory (converted if not; the stem also takes
-    plain NCHW).  Returns a channels_last tensor, or NCHW tensor(s) when ``nchw_out`` (heads)."""
+    plain NCHW).  Returns a channels_last tensor, or NCHW tensor(s) when ``nchw_out`` (heads).  ``y`` (and ``y2`` for the
+    second part of a ``split`` head): the caller's own output buffers instead of fresh ones."""
     N.require_device(x, "conv")
     act = pack.act if act is None else act
     n, c, h, w = (int(v) for v in x.shape)
@@ -837,15 +854,16 @@ def conv_native(x, pack, act=None, residual=None, nchw_out=False, split=None, ac
     elif not x.is_contiguous(memory_format=torch.channels_last):
         x = x.contiguous(memory_format=torch.channels_last)
     ho, wo = _out_hw(h, w, pack.k, pack.stride)
-    y2 = None
+    if y2 is not None and not (nchw_out and split is not None):
+        raise N.SsdkError("conv: y2 is the second output of a split NCHW head; this call has none")
     if nchw_out:
         if split is not None:
-            y = torch.empty((n, split, ho, wo), device=x.device, dtype=x.dtype)
-            y2 = torch.empty((n, pack.cout - split, ho, wo), device=x.device, dtype=x.dtype)
+            y = _out_tensor(y, (n, split, ho, wo), x, torch.contiguous_format, "conv")
+            y2 = _out_tensor(y2, (n, pack.cout - split, ho, wo), x, torch.contiguous_format, "conv (y2)")
         else:
-            y = torch.empty((n, pack.cout, ho, wo), device=x.device, dtype=x.dtype)
+            y = _out_tensor(y, (n, pack.cout, ho, wo), x, torch.contiguous_format, "conv")
     else:
-        y = torch.empty((n, pack.cout, ho, wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+        y = _out_tensor(y, (n, pack.cout, ho, wo), x, torch.channels_last, "conv")
     if residual is not None and not residual.is_contiguous(memory_format=torch.channels_last):
         residual = residual.contiguous(memory_format=torch.channels_last)
     d = fill_desc(N.ConvDesc(), x.data_ptr(), n, h, w, pack, N.dtype_code(x), act, y.data_ptr(), in_layout,

@@ -10,6 +10,7 @@ the floor of PyTorch-ROCm running the same module in the same dtype; there is no
 import pytest
 
 import cases_yolo
+import guardband as G
 import nethelp
 
 pytestmark = pytest.mark.gpu
@@ -112,28 +113,6 @@ def test_spp_equals_the_torch_expression(i, dtype):
         assert torch.equal(y[:, s * c:(s + 1) * c], want[:, s * c:(s + 1) * c]), "spp %s %s window %d" % (SPP_CASES[i], dtype, k)
 
 
-GUARD = 4096  # elements on either side (keeps the 16-byte alignment)
-
-
-def _guarded(shape_nchw, dtype, fill=None):
-    """A channels_last tensor of ``shape_nchw`` between two guards of NaNs -> (the flat storage, the view)."""
-    import torch
-
-    n, c, h, w = shape_nchw
-    numel = n * c * h * w
-    flat = torch.full((GUARD + numel + GUARD,), float("nan"), dtype=dtype, device="cuda")
-    inner = flat[GUARD:GUARD + numel].view(n, h, w, c).permute(0, 3, 1, 2)
-    if fill is not None:
-        inner.copy_(fill)
-    return flat, inner
-
-
-def _bits(t):
-    import torch
-
-    return t.view(torch.int16)
-
-
 @pytest.mark.parametrize("i,dtype", [(1, "bfloat16"), (2, "float16"), (4, "float16")])
 def test_cat2_writes_y_and_nothing_else(i, dtype):
     """a, b and y sit between NaN guards: every element of y is written, nothing outside it, the sources are not written, and
@@ -144,15 +123,15 @@ def test_cat2_writes_y_and_nothing_else(i, dtype):
     tdt = getattr(torch, dtype)
     n, h, w, c1, c2, up2 = CAT_CASES[i]
     a, b = _cat_operands(CAT_CASES[i], tdt, seed=9)
-    aflat, ag = _guarded(a.shape, tdt, a)
-    bflat, bg = _guarded(b.shape, tdt, b)
-    yflat, y = _guarded((n, c1 + c2, h, w), tdt)
-    before = [_bits(t).clone() for t in (aflat, bflat, yflat)]
+    gs = G.GuardSet("cuda")  # (tests/guardband.py: views between NaN guards; inputs are snapshotted)
+    cl = lambda t: t.cuda().contiguous(memory_format=torch.channels_last)  # noqa: E731
+    ag, bg = gs.inp("a", cl(a)), gs.inp("b", cl(b))
+    y = gs.out("y", (n, c1 + c2, h, w), tdt, torch.channels_last)
+    gs.arm()
     out = FC.cat_native(ag, bg, up2=up2, y=y)
     torch.cuda.synchronize()
     assert out.data_ptr() == y.data_ptr()
-    assert torch.equal(_bits(aflat), before[0]) and torch.equal(_bits(bflat), before[1]), "a source was written"
-    assert torch.equal(_bits(yflat)[:GUARD], before[2][:GUARD]) and torch.equal(_bits(yflat)[-GUARD:], before[2][-GUARD:])
+    assert gs.problems() == [], "a source or a guard was written"
     assert not torch.isnan(y).any(), "an element of y was not written, or a guard was read"
     assert torch.equal(y, _cat_want(a, b, up2))
 
@@ -165,14 +144,14 @@ def test_spp_writes_y_and_nothing_else(i, dtype):
     tdt = getattr(torch, dtype)
     n, h, w, c = SPP_CASES[i]
     x = _spp_operand(SPP_CASES[i], tdt, seed=9)
-    xflat, xg = _guarded(x.shape, tdt, x)
-    yflat, y = _guarded((n, 4 * c, h, w), tdt)
-    before = [_bits(t).clone() for t in (xflat, yflat)]
+    gs = G.GuardSet("cuda")
+    xg = gs.inp("x", x.cuda().contiguous(memory_format=torch.channels_last))
+    y = gs.out("y", (n, 4 * c, h, w), tdt, torch.channels_last)
+    gs.arm()
     out = FC.spp_native(xg, y=y)
     torch.cuda.synchronize()
     assert out.data_ptr() == y.data_ptr()
-    assert torch.equal(_bits(xflat), before[0]), "x was written"
-    assert torch.equal(_bits(yflat)[:GUARD], before[1][:GUARD]) and torch.equal(_bits(yflat)[-GUARD:], before[1][-GUARD:])
+    assert gs.problems() == [], "x or a guard was written"
     assert not torch.isnan(y).any(), "an element of y was not written, or a guard was read"
     assert torch.equal(y, _spp_want(x))
 

@@ -11,6 +11,7 @@ tests/test_gpu_nets.py -- the floor of PyTorch-ROCm running the same module in t
 import pytest
 
 import cases_shelf
+import guardband as G
 import nethelp
 
 pytestmark = pytest.mark.gpu
@@ -116,30 +117,16 @@ def test_nothing_outside_the_output_is_written(i, with_skip):
     m, x, s = _operands(n, cin, cout, h, w, with_skip, bias, dtype, seed=9)
     want = _want(m, x, s)
     ho, wo = 2 * h - 1, 2 * w - 1
-    numel, guard = n * ho * wo * cout, 4096  # (the guard keeps the 16-byte alignment)
-
-    def guarded(fill):
-        flat = torch.full((guard + numel + guard,), float("nan"), dtype=dtype, device="cuda")
-        inner = flat[guard:guard + numel].view(n, ho, wo, cout).permute(0, 3, 1, 2)
-        if fill is not None:
-            inner.copy_(fill.cuda())
-        return flat, inner
-
-    yflat, y = guarded(None)
-    bits = lambda t: t.view(torch.int16)
-    before = bits(yflat).clone()
-    sk = None
-    if with_skip:
-        sflat, sk = guarded(s)
-        sbefore = bits(sflat).clone()
+    gs = G.GuardSet("cuda")  # (tests/guardband.py: views between NaN guards; inputs are snapshotted)
+    y = gs.out("y", (n, cout, ho, wo), dtype, torch.channels_last)
+    sk = gs.inp("skip", s.cuda().contiguous(memory_format=torch.channels_last)) if with_skip else None
+    gs.arm()
     pk = FC.ConvTPack(m.cuda(), dtype)
     out = FC.convt_native(x.cuda().contiguous(memory_format=torch.channels_last), pk, sk, y=y)
     torch.cuda.synchronize()
     assert out.data_ptr() == y.data_ptr()
-    assert torch.equal(bits(yflat)[:guard], before[:guard]) and torch.equal(bits(yflat)[guard + numel:], before[guard + numel:])
+    assert gs.problems() == [], "a guard of y or of skip, or skip itself, was written"
     assert not torch.isnan(y).any(), "an element of y was not written, or a skip guard was read"
-    if with_skip:
-        assert torch.equal(bits(sflat), sbefore), "skip was written"
     _rounding_bar(y, want, 2.0 ** -10 if i % 2 else 2.0 ** -8, "guarded convt %s" % (CASES[i],))
 
 

@@ -7,6 +7,8 @@ import sys
 
 import pytest
 
+import guardband as G
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -195,11 +197,10 @@ def test_padding_is_inert(gw, groups, stride):
     pack = FC.ConvPack(conv.cuda(), bn.cuda(), "relu", dtype)
     xs = torch.randn(n, h, w, c).to(dtype)  # NHWC values
     per = h * w * c
-    guard = 4096 + per                      # (a multiple of 8 elements: the view stays 16-byte aligned)
-    big = torch.full((guard + n * per + guard,), float("nan"), dtype=dtype, device="cuda")
-    big[guard:guard + n * per] = xs.reshape(-1).cuda()
-    view = big[guard:guard + n * per].view(n, h, w, c).permute(0, 3, 1, 2)  # [N,C,H,W] in channels_last memory, no copy
-    assert view.is_contiguous(memory_format=torch.channels_last) and view.data_ptr() == big.data_ptr() + 2 * guard
+    # (tests/guardband.py: 4096 elements + one image of 0xFF bytes -- NaN -- on either side; [N,C,H,W] in channels_last memory)
+    big, view = G.guarded(xs.cuda().permute(0, 3, 1, 2))
+    assert view.is_contiguous(memory_format=torch.channels_last) and view.data_ptr() - big.data_ptr() >= 2 * (4096 + per)
+    assert bool(torch.isnan(big.view(dtype)[:4096 + per]).all())
     y_view = FC.conv_native(view, pack)
     clean = xs.cuda().permute(0, 3, 1, 2)
     y_clean = FC.conv_native(clean, pack)
