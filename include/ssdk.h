@@ -923,10 +923,17 @@ size_t ssdk_mbse_desc_bytes(void);
  *        [N][H/2][W/2][C2], nearest x2 (SSDK_FUSE_UP2), else [N][H][W][C2] (SSDK_FUSE_SAME);  k = 1, stride = 1
  *   SPP  x [N][H][W][C], y [N][H][W][4C];  Cin = C, Cout = 4 C;  k = 5, stride = 1;  residual NULL, res_mode 0
  * N, H, W, dtype as in the descriptors; in_layout = out_layout = SSDK_LAYOUT_NHWC, groups <= 1, act SSDK_ACT_NONE; w, scale, bias,
- * y2 and w_frag must be NULL.  Anything else: SSDK_E_BADARG. */
+ * y2 and w_frag must be NULL.  Anything else: SSDK_E_BADARG.
+ *
+ * SSDK_OP_DKRES (executor op kind 10, lane 0 only): the DarkNet residual block x + act2(BN(conv3x3(act1(BN(conv1x1(x)))))) as one
+ * launch, ssdk_dkres of include/ssdk_dkres.h.  It brings no member to ssdk_op either and is described by `xpair`, read as
+ *   x, y         NHWC input and output, both [N][H][W][C] (no stride: the output has the input's size); y must not overlap x
+ *   Cin = Cout = C, Cmid = C / 2 (anything else: SSDK_E_BADARG)
+ *   w1, scale1, bias1, w2, scale2, bias2, act1, act2, w1_frag, w2_frag, N, H, W, dtype as named in ssdk_dkres_desc. */
 enum { SSDK_OP_CONV = 0, SSDK_OP_MBCONV = 1, SSDK_OP_FUSE = 2, SSDK_OP_STEM7 = 3, SSDK_OP_POOL = 4, SSDK_OP_XPAIR = 5,
        SSDK_OP_MBSE = 6 /* lane 0 only */, SSDK_OP_CONVT = 7 /* lane 0 only; described by `conv`, see above */,
-       SSDK_OP_CAT = 8, SSDK_OP_SPP = 9 /* both lane 0 only; described by `conv`, see above */ };
+       SSDK_OP_CAT = 8, SSDK_OP_SPP = 9 /* both lane 0 only; described by `conv`, see above */,
+       SSDK_OP_DKRES = 10 /* lane 0 only; described by `xpair`, see above */ };
 typedef struct ssdk_op {
   int32_t kind, lane;
   ssdk_conv_desc conv;

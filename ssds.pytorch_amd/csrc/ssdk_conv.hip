@@ -28,6 +28,7 @@
 #include "ssdk_ctx.h"
 #include "../../include/ssdk_convt.h"
 #include "../../include/ssdk_cat.h"
+#include "../../include/ssdk_dkres.h"
 
 namespace ssdk {
 
@@ -1539,6 +1540,20 @@ static int run_cat_op(const ssdk_conv_desc* c, bool spp, hipStream_t st) {
   return ssdk_cat2(&d, st);
 }
 
+// SSDK_OP_DKRES: the op's ssdk_xpair_desc read as a DarkNet residual block (include/ssdk.h) -> ssdk_dkres
+static int run_dkres_op(const ssdk_xpair_desc* x, hipStream_t st) {
+  if (x->Cin != x->Cout || x->Cin != 2 * (long long)x->Cmid) {
+    set_error("dkres op: Cin=%d Cmid=%d Cout=%d (Cin = Cout = C, Cmid = C / 2)", x->Cin, x->Cmid, x->Cout);
+    return SSDK_E_BADARG;
+  }
+  ssdk_dkres_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x = x->x, d.y = x->y, d.w1 = x->w1, d.scale1 = x->scale1, d.bias1 = x->bias1, d.w2 = x->w2, d.scale2 = x->scale2, d.bias2 = x->bias2;
+  d.w1_frag = x->w1_frag, d.w2_frag = x->w2_frag;
+  d.N = x->N, d.H = x->H, d.W = x->W, d.C = x->Cin, d.act1 = x->act1, d.act2 = x->act2, d.dtype = x->dtype;
+  return ssdk_dkres(&d, st);
+}
+
 extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* workspace, size_t workspace_bytes,
                                 void* stream) {
   if (int rc = ssdk::ctx_enter(ctx)) return rc;
@@ -1646,6 +1661,7 @@ extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* 
       else if (ops[i].kind == SSDK_OP_CONVT && ops[i].lane == 0) rc = run_convt_op(&ops[i].conv, st);
       else if ((ops[i].kind == SSDK_OP_CAT || ops[i].kind == SSDK_OP_SPP) && ops[i].lane == 0)
         rc = run_cat_op(&ops[i].conv, ops[i].kind == SSDK_OP_SPP, st);
+      else if (ops[i].kind == SSDK_OP_DKRES && ops[i].lane == 0) rc = run_dkres_op(&ops[i].xpair, st);
       else {
         set_error("unknown op kind %d", ops[i].kind);
         rc = SSDK_E_BADARG;

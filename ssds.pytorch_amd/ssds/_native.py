@@ -168,8 +168,8 @@ F32, BF16, F16 = _K["SSDK_F32"], _K["SSDK_BF16"], _K["SSDK_F16"]
 ACT = {n: _K["SSDK_ACT_" + n.upper()] for n in ("none", "relu", "relu6", "silu", "sigmoid")}
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 U8 = _K["SSDK_U8"]  # ssdk_preprocess source only
-OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE, OP_CONVT, OP_CAT, OP_SPP = (
-    _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE", "CONVT", "CAT", "SPP"))
+OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE, OP_CONVT, OP_CAT, OP_SPP, OP_DKRES = (
+    _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE", "CONVT", "CAT", "SPP", "DKRES"))
 MBSE_DW, MBSE_GATE, MBSE_PROJ = 1, 2, 4  # ssdk_mbse_desc.stages bits (0 = all three); the header has no names for them
 FUSE_SAME, FUSE_UP2, FUSE_POOL2 = _K["SSDK_FUSE_SAME"], _K["SSDK_FUSE_UP2"], _K["SSDK_FUSE_POOL2"]
 NCHW, NHWC = _K["SSDK_LAYOUT_NCHW"], _K["SSDK_LAYOUT_NHWC"]
@@ -204,6 +204,18 @@ CatDesc, SppDesc = _HC.structs["ssdk_cat_desc"], _HC.structs["ssdk_spp_desc"]
 CatDesc.__doc__ = "ssdk_cat_desc: y = a || b, or a || nearest_x2(b), along the channels (YOLOv3 / PAN concatenations)."
 SppDesc.__doc__ = "ssdk_spp_desc: y = x || maxpool5(x) || maxpool9(x) || maxpool13(x) (the SPP block of YOLOv4)."
 
+# include/ssdk_dkres.h: the DarkNet residual block as one launch, a header of its own for the same reason
+DKRES_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_dkres.h")
+if not os.path.exists(DKRES_HEADER_PATH):
+    raise ImportError("include/ssdk_dkres.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_dkres from it".format(
+        DKRES_HEADER_PATH))
+with open(DKRES_HEADER_PATH) as _f:
+    _HD = parse_header(_f.read(), {"ssdk_dkres_desc": "DkresDesc"})
+DKRES_EXPORTS = tuple(_HD.functions)
+DkresDesc = _HD.structs["ssdk_dkres_desc"]
+DkresDesc.__doc__ = "ssdk_dkres_desc: y = x + act2(bn2(conv3x3(act1(bn1(conv1x1(x)))))), the DarkNet residual block in one launch."
+DKRES_TILE_H, DKRES_TILE_W = _HD.constants["SSDK_DKRES_TILE_H"], _HD.constants["SSDK_DKRES_TILE_W"]  # a workgroup's output tile
+
 # include/ssdk_cattrain.h: the same two operations of the YOLO TRAINING step, forward and backward on NCHW tensors (no descriptors)
 CATTRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_cattrain.h")
 if not os.path.exists(CATTRAIN_HEADER_PATH):
@@ -230,7 +242,7 @@ def _load():
     def bind(name):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions.get(name) or _HC.functions.get(name)
-                                   or _HCT.functions.get(name) or _HTT.functions[name])
+                                   or _HD.functions.get(name) or _HCT.functions.get(name) or _HTT.functions[name])
         return fn
 
     # version FIRST: a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from the symbol lookup
@@ -242,11 +254,11 @@ def _load():
     if have < ABI_VERSION:
         raise ImportError("libssdk.so at {} is ABI {} but ssds/_native.py is written for ABI {}: rebuild it "
                           "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, have, ABI_VERSION))
-    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS + CATTRAIN_EXPORTS + CONVTTRAIN_EXPORTS:
+    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS + DKRES_EXPORTS + CATTRAIN_EXPORTS + CONVTTRAIN_EXPORTS:
         try:
             bind(name)
         except AttributeError:
-            raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h (or ssdk_convt.h, ssdk_cat.h, "
+            raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h (or ssdk_convt.h, ssdk_cat.h, ssdk_dkres.h, "
                               "ssdk_cattrain.h, ssdk_convttrain.h next to it) declares: rebuild it "
                               "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, name))
     # the ctypes mirrors must have the layout the library was BUILT with: a shorter struct would be read past its end.
@@ -263,9 +275,10 @@ def _load():
     # ssdk_struct_size (its eight indices are part of ABI 245): the library reports their sizes itself
     mirrors = dict(_H.structs, **_HT.structs)
     mirrors.update(_HC.structs)
+    mirrors.update(_HD.structs)
     for cname, fn in (("ssdk_augment_desc", lib.ssdk_augment_desc_bytes), ("ssdk_mbse_desc", lib.ssdk_mbse_desc_bytes),
                       ("ssdk_convt_desc", lib.ssdk_convt_desc_bytes), ("ssdk_cat_desc", lib.ssdk_cat_desc_bytes),
-                      ("ssdk_spp_desc", lib.ssdk_spp_desc_bytes)):
+                      ("ssdk_spp_desc", lib.ssdk_spp_desc_bytes), ("ssdk_dkres_desc", lib.ssdk_dkres_desc_bytes)):
         if int(fn()) != ctypes.sizeof(mirrors[cname]):
             raise ImportError("libssdk.so at {} has sizeof({}) = {} but ssds/_native.py mirrors it with {} bytes: "
                               "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, cname, int(fn()),

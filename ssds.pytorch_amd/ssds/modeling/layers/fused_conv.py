@@ -750,6 +750,64 @@ def xpair_native(x, p1, p2, y=None):
     return y
 
 
+# ---- DarkNet residual block (csrc/ssdk_dkres.hip): 1x1 + BN + act -> 3x3 + BN + act -> + x as one launch, the middle map in LDS ----
+# Widths routed to the fused kernel when SSDK_DKRES is unset: those the probe (tools/dkres_probe.py) measured not slower
+# than the two ssdk_conv launches at the shipped configs' batch-32 shapes.  SSDK_DKRES=1: every width ssdk_dkres_supported takes;
+# SSDK_DKRES=0: none (every block is two launches).
+DKRES_DEFAULT_WIDTHS = (64, 128, 256)
+
+
+def dkres_supported(p1, p2, h, w, dtype_code=None):
+    """A residual block (``p1``: 1x1, C -> C/2; ``p2``: 3x3 / stride 1, C/2 -> C; both dense with a folded BatchNorm and none / relu
+    / relu6) that csrc/ssdk_dkres.hip runs as one launch.  The shapes are the C predicate's to decide (``ssdk_dkres_supported``);
+    ``SSDK_DKRES`` (read at every call) narrows or widens the widths that are routed to it."""
+    if not (p1.kind == "dense" and p2.kind == "dense" and p1.k == 1 and p1.stride == 1 and p2.k == 3 and p2.stride == 1
+            and p1.cout == p2.cin and p2.cout == p1.cin and p1.cin == 2 * p1.cout
+            and p1.act in ("none", "relu", "relu6") and p2.act in ("none", "relu", "relu6")
+            and p1.scale is not None and p2.scale is not None and p1.w.dtype == p2.w.dtype):
+        return False
+    if dtype_code is None:
+        dtype_code = N._DTYPES.get(p1.w.dtype, -1)
+    if not N.lib.ssdk_dkres_supported(p1.cin, h, w, dtype_code):
+        return False
+    env = os.environ.get("SSDK_DKRES")
+    if env is None:
+        return p1.cin in DKRES_DEFAULT_WIDTHS
+    return env != "0"
+
+
+def fill_dkres_desc(d, x_ptr, y_ptr, n, h, w, p1, p2, dtype_code):
+    """Fills an ``ssdk_dkres_desc`` -- or the ``ssdk_xpair_desc`` of an SSDK_OP_DKRES op (include/ssdk.h: Cin = Cout = C,
+    Cmid = C / 2), whose other fields carry the same names."""
+    d.x, d.y = x_ptr, y_ptr
+    d.w1, d.scale1, d.bias1 = p1.w.data_ptr(), p1.scale.data_ptr(), p1.bias.data_ptr()
+    d.w2, d.scale2, d.bias2 = p2.w.data_ptr(), p2.scale.data_ptr(), p2.bias.data_ptr()
+    f1, f2 = p1.frag(), p2.frag()
+    d.w1_frag, d.w2_frag = (f1.data_ptr(), f2.data_ptr()) if f1 is not None and f2 is not None else (None, None)
+    d.N, d.H, d.W = n, h, w
+    if isinstance(d, N.XpairDesc):
+        d.Cin, d.Cmid, d.Cout = p1.cin, p1.cout, p2.cout
+    else:
+        d.C = p1.cin
+    d.act1, d.act2, d.dtype = N.ACT[p1.act], N.ACT[p2.act], dtype_code
+    return d
+
+
+def dkres_native(x, p1, p2, y=None):
+    """``x + act2(bn2(conv3x3(act1(bn1(conv1x1(x))))))`` in one launch; x channels_last (``y``: write there; never ``x`` itself --
+    a workgroup reads its neighbours' ``x``)."""
+    N.require_device(x, "dkres")
+    x = _channels_last(x)
+    n, c, h, w = (int(v) for v in x.shape)
+    y = _out_tensor(y, (n, c, h, w), x, torch.channels_last, "dkres")
+    d = fill_dkres_desc(N.DkresDesc(), x.data_ptr(), y.data_ptr(), n, h, w, p1, p2, N.dtype_code(x))
+    with torch.cuda.device(x.device):
+        rc = N.lib.ssdk_dkres(ctypes.byref(d), N.stream_ptr(x.device))
+    N.check(rc, "dkres")
+    STATS["native_layers"] += 2
+    return y
+
+
 def fuse_native(a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_c=N.FUSE_SAME, y=None):
     """y = w0*a + w1*R_b(b) [+ w2*R_c(c)] (BiFPN weighted fusion, csrc/ssdk_fuse.hip); channels_last tensors (``y``: write
     there)."""
@@ -1062,6 +1120,16 @@ class ConvPlan(object):
         self.keep.extend([p1, p2])
         return (out, n, p2.cout, ho, wo)
 
+    def dkres(self, val, p1, p2):
+        """A DarkNet residual block as one op (csrc/ssdk_dkres.hip): [n, c, h, w] -> [n, c, h, w].  The output is a buffer of its
+        own -- the arena never hands out ``val``'s while ``val`` is unreleased, and the kernel refuses y == x."""
+        buf, n, c, h, w = val
+        assert c == p1.cin == p2.cout and p1.cout == p2.cin, (c, p1.cin, p1.cout, p2.cin, p2.cout)
+        out = self.arena.get(n * c * h * w * self.es)
+        self.layers.append(dict(kind="dkres", x=buf, n=n, h=h, w=w, pack=p1, pack2=p2, y=out))
+        self.keep.extend([p1, p2])
+        return (out, n, c, h, w)
+
     def stem7(self, val, pack):
         buf, n, c, h, w = val
         ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
@@ -1186,6 +1254,11 @@ class ConvPlan(object):
                 fill_xpair_desc(op.xpair, self._ptr(L["x"], self.patches, i, "xpair.x"), self.arena.ptr(L["y"]), L["n"], L["h"],
                                 L["w"], L["pack"], L["pack2"], self.dtype_code)
                 continue
+            if kind == "dkres":  # carried by the op's ssdk_xpair_desc (include/ssdk.h SSDK_OP_DKRES)
+                op.kind = N.OP_DKRES
+                fill_dkres_desc(op.xpair, self._ptr(L["x"], self.patches, i, "xpair.x"), self.arena.ptr(L["y"]), L["n"], L["h"],
+                                L["w"], L["pack"], L["pack2"], self.dtype_code)
+                continue
             if kind == "stem7":
                 op.kind = N.OP_STEM7
                 st, pk = op.stem, L["pack"]
@@ -1283,6 +1356,13 @@ class ConvPlan(object):
                 macs = n * (h * w * pk.cin * pk.cout + ho * wo * 9 * p2.cin * p2.cout)
                 byt = es * (n * (h * w * pk.cin + ho * wo * p2.cout) + pk.cin * pk.cout + 9 * p2.cin * p2.cout)
                 rows.append(dict(name="extra %d>%d>%d k1,k3s2 @%dx%d" % (pk.cin, pk.cout, p2.cout, h, w), flops=2.0 * macs,
+                                 bytes=float(byt), kind="conv"))
+                continue
+            if L.get("kind") == "dkres":  # both convolutions' MACs; x in and y out once (mid never leaves the CU), the weights
+                p2 = L["pack2"]
+                macs = n * h * w * (pk.cin * pk.cout + 9 * p2.cin * p2.cout)
+                byt = es * (n * h * w * (pk.cin + p2.cout) + pk.cin * pk.cout + 9 * p2.cin * p2.cout)
+                rows.append(dict(name="dkres %d>%d>%d k1,k3 @%dx%d" % (pk.cin, pk.cout, p2.cout, h, w), flops=2.0 * macs,
                                  bytes=float(byt), kind="conv"))
                 continue
             if L.get("kind") == "mb":

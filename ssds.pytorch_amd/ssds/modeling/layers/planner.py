@@ -11,8 +11,8 @@ import torch.nn as nn
 
 import os
 
-from .fused_conv import (ConvPack, ConvPlan, ConvTPack, MbPack, MbSePack, StemPack, cat_supported, conv_kind, pack_heads, sequential_groups,
-                         xpair_supported)
+from .fused_conv import (ConvPack, ConvPlan, ConvTPack, MbPack, MbSePack, StemPack, cat_supported, conv_kind, dkres_supported, pack_heads,
+                         sequential_groups, xpair_supported)
 
 
 class PlanUnsupported(Exception):
@@ -284,9 +284,73 @@ def record_efficientnet(plan, val, net):
     return outputs
 
 
+def _darknet_group(module, kinds, what):
+    """(conv, bn, act) of one Conv-BN-ReLU6 group of the DarkNet backbone; PlanUnsupported, with the reason, for anything else."""
+    groups = sequential_groups(nn.Sequential(*flatten(module)))
+    if groups is None or len(groups) != 1:
+        raise PlanUnsupported("DarkNet {}: one Conv + BatchNorm + ReLU6 group expected, found {}".format(
+            what, [type(m).__name__ for m in flatten(module)]))
+    conv, bn, act = groups[0]
+    if bn is None or act != "relu6":
+        raise PlanUnsupported("DarkNet {}: Conv + BatchNorm + ReLU6 expected, found {} / {} / {}".format(
+            what, type(conv).__name__, type(bn).__name__, act))
+    if conv_kind(conv) not in kinds:
+        raise PlanUnsupported("DarkNet {}: conv not covered by the HIP kernels ({} expected): {}".format(what, " | ".join(kinds), conv))
+    return conv, bn, act
+
+
+def record_darknet(plan, val, net):
+    """DarkNet53 (nets/darknet.py): the stride-1 3 -> 32 image convolution on the image-stem kernel (its bias folded with the
+    BatchNorm by fold_bn), each stage's stride-2 3x3 as a dense conv, and each Residual as ONE dkres op (csrc/ssdk_dkres.hip)
+    where ``dkres_supported`` takes it -- otherwise two convs, the second adding x behind its activation (res_mode 0)."""
+    from ssds.modeling.nets.darknet import DarkNet, Residual
+
+    if not isinstance(net, DarkNet):
+        raise PlanUnsupported("backbone {} has no planner".format(type(net).__name__))
+    dt = plan.dtype
+    sconv, sbn, sact = _darknet_group(net.conv1, ("stem",), "conv1")
+    if sconv.stride != (1, 1):
+        raise PlanUnsupported("DarkNet conv1: stride 1 expected, found {}".format(sconv.stride))
+    cur = plan.conv(val, ConvPack(sconv, sbn, sact, dt))  # (the image is not an arena buffer)
+    outputs = []
+    for level in range(1, 6):
+        if level > max(net.outputs):
+            break
+        for j, blk in enumerate(getattr(net, "block{}".format(level))):
+            keep_cur = any(cur is o for o in outputs)
+            what = "block{}.{}".format(level, j)
+            if j == 0:
+                conv, bn, act = _darknet_group(blk, ("dense",), what)
+                if conv.kernel_size != (3, 3) or conv.stride != (2, 2):
+                    raise PlanUnsupported("DarkNet {}: a 3x3 / stride 2 convolution expected: {}".format(what, conv))
+                out = plan.conv(cur, ConvPack(conv, bn, act, dt))
+            elif isinstance(blk, Residual):
+                c1, b1, a1 = _darknet_group(blk.conv1x1, ("dense",), what + ".conv1x1")
+                c2, b2, a2 = _darknet_group(blk.conv3x3, ("dense",), what + ".conv3x3")
+                if (c1.kernel_size != (1, 1) or c2.kernel_size != (3, 3) or c1.stride != (1, 1) or c2.stride != (1, 1)
+                        or c2.out_channels != c1.in_channels):
+                    raise PlanUnsupported("DarkNet {}: 1x1 then 3x3, both stride 1, C -> C/2 -> C expected".format(what))
+                p1, p2 = ConvPack(c1, b1, a1, dt), ConvPack(c2, b2, a2, dt)
+                if dkres_supported(p1, p2, cur[3], cur[4], plan.dtype_code):
+                    out = plan.dkres(cur, p1, p2)
+                else:
+                    mid = plan.conv(cur, p1)
+                    out = plan.conv(mid, p2, residual=cur, res_mode=0)
+                    plan.release(mid)
+            else:
+                raise PlanUnsupported("DarkNet {}: block {} has no planner".format(what, type(blk).__name__))
+            if not keep_cur:
+                plan.release(cur)
+            cur = out
+        if level in net.outputs:
+            outputs.append(cur)
+    return outputs
+
+
 def record_backbone(plan, val, net):
-    """Backbone maps of a planned backbone (MobileNet, ResNet, RegNetX, EfficientNet) from the image value; PlanUnsupported
-    otherwise."""
+    """Backbone maps of a planned backbone (MobileNet, ResNet, RegNetX, EfficientNet, DarkNet) from the image value;
+    PlanUnsupported otherwise."""
+    from ssds.modeling.nets.darknet import DarkNet
     from ssds.modeling.nets.efficientnet import EfficientEx
     from ssds.modeling.nets.mobilenet import MobileNetEx
     from ssds.modeling.nets.regnet import RegNet
@@ -300,6 +364,8 @@ def record_backbone(plan, val, net):
         return record_resnet(plan, val, net)
     if isinstance(net, RegNet):
         return record_regnet(plan, val, net)
+    if isinstance(net, DarkNet):
+        return record_darknet(plan, val, net)
     raise PlanUnsupported("backbone {} has no planner".format(type(net).__name__))
 
 
