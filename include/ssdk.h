@@ -929,11 +929,29 @@ size_t ssdk_mbse_desc_bytes(void);
  * launch, ssdk_dkres of include/ssdk_dkres.h.  It brings no member to ssdk_op either and is described by `xpair`, read as
  *   x, y         NHWC input and output, both [N][H][W][C] (no stride: the output has the input's size); y must not overlap x
  *   Cin = Cout = C, Cmid = C / 2 (anything else: SSDK_E_BADARG)
- *   w1, scale1, bias1, w2, scale2, bias2, act1, act2, w1_frag, w2_frag, N, H, W, dtype as named in ssdk_dkres_desc. */
+ *   w1, scale1, bias1, w2, scale2, bias2, act1, act2, w1_frag, w2_frag, N, H, W, dtype as named in ssdk_dkres_desc.
+ *
+ * SSDK_OP_DENSE / SSDK_OP_DENSEPOOL / SSDK_OP_DENSEPLACE (executor op kinds 11, 12, 13, lane 0 only): the DenseNet dense layer as
+ * one launch, the front of a transition and the copy into a dense block's buffer -- ssdk_dense_layer / ssdk_dense_pool /
+ * ssdk_dense_place of include/ssdk_denselayer.h.  They bring no member to ssdk_op either.
+ *   DENSE is described by `xpair`, read as
+ *     x, y           pixel-0 pointers of the Cin channels read and of the 32 channels written, both with pixel stride `pad` (= ld)
+ *                    channels; inside a block y = x + Cin elements
+ *     Cin, Cmid = 128, Cout = 32, act1 = SSDK_ACT_RELU, act2 = SSDK_ACT_NONE (anything else: SSDK_E_BADARG)
+ *     scale2, bias2  the fp32 pair (a, b) of the folded norm1, [Cin] each: nothing follows the 3x3, so the members are free
+ *     w1, scale1, bias1, w2, w1_frag, w2_frag, N, H, W, dtype as named in ssdk_dense_layer_desc
+ *   DENSEPOOL and DENSEPLACE are described by `conv`, read as
+ *     POOL   x buffer of pixel stride `split` (= ld) [N][H][W], channels [0, C); y dense [N][H/2][W/2][C]; scale, bias = (a, b);
+ *            Cin = Cout = C, k = stride = 2, act SSDK_ACT_RELU
+ *     PLACE  x dense [N][H][W][C]; y buffer of pixel stride `split` (= ld), channels [0, C); Cin = Cout = C, k = stride = 1,
+ *            act SSDK_ACT_NONE, scale and bias NULL
+ *     in_layout = out_layout = SSDK_LAYOUT_NHWC, groups <= 1, res_mode 0; w, residual, y2 and w_frag NULL. */
 enum { SSDK_OP_CONV = 0, SSDK_OP_MBCONV = 1, SSDK_OP_FUSE = 2, SSDK_OP_STEM7 = 3, SSDK_OP_POOL = 4, SSDK_OP_XPAIR = 5,
        SSDK_OP_MBSE = 6 /* lane 0 only */, SSDK_OP_CONVT = 7 /* lane 0 only; described by `conv`, see above */,
        SSDK_OP_CAT = 8, SSDK_OP_SPP = 9 /* both lane 0 only; described by `conv`, see above */,
-       SSDK_OP_DKRES = 10 /* lane 0 only; described by `xpair`, see above */ };
+       SSDK_OP_DKRES = 10 /* lane 0 only; described by `xpair`, see above */,
+       SSDK_OP_DENSE = 11 /* lane 0 only; described by `xpair`, see above */,
+       SSDK_OP_DENSEPOOL = 12, SSDK_OP_DENSEPLACE = 13 /* both lane 0 only; described by `conv`, see above */ };
 typedef struct ssdk_op {
   int32_t kind, lane;
   ssdk_conv_desc conv;

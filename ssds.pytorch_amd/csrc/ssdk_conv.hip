@@ -29,6 +29,7 @@
 #include "../../include/ssdk_convt.h"
 #include "../../include/ssdk_cat.h"
 #include "../../include/ssdk_dkres.h"
+#include "../../include/ssdk_denselayer.h"
 
 namespace ssdk {
 
@@ -1554,6 +1555,46 @@ static int run_dkres_op(const ssdk_xpair_desc* x, hipStream_t st) {
   return ssdk_dkres(&d, st);
 }
 
+// SSDK_OP_DENSE: the op's ssdk_xpair_desc read as a DenseNet dense layer (include/ssdk.h) -> ssdk_dense_layer
+static int run_dense_op(const ssdk_xpair_desc* x, hipStream_t st) {
+  if (x->Cmid != SSDK_DENSE_CMID || x->Cout != SSDK_DENSE_COUT || x->act1 != SSDK_ACT_RELU || x->act2 != SSDK_ACT_NONE) {
+    set_error("dense op: Cmid=%d Cout=%d act1=%d act2=%d (Cmid 128, Cout 32, act1 relu, act2 none)", x->Cmid, x->Cout, x->act1, x->act2);
+    return SSDK_E_BADARG;
+  }
+  ssdk_dense_layer_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x = x->x, d.y = x->y, d.w1 = x->w1, d.a = x->scale2, d.b = x->bias2, d.scale1 = x->scale1, d.bias1 = x->bias1, d.w2 = x->w2;
+  d.w1_frag = x->w1_frag, d.w2_frag = x->w2_frag;
+  d.N = x->N, d.H = x->H, d.W = x->W, d.Cin = x->Cin, d.ld = x->pad, d.dtype = x->dtype;
+  return ssdk_dense_layer(&d, st);
+}
+
+// SSDK_OP_DENSEPOOL / SSDK_OP_DENSEPLACE: the op's ssdk_conv_desc read as the front of a transition / the copy into a block's
+// buffer (include/ssdk.h) -> ssdk_dense_pool / ssdk_dense_place
+static int run_dense_aux_op(const ssdk_conv_desc* c, bool pool, hipStream_t st) {
+  const char* what = pool ? "densepool" : "denseplace";
+  if (c->w || c->residual || c->y2 || c->w_frag || c->in_layout != LAYOUT_NHWC || c->out_layout != LAYOUT_NHWC || c->groups > 1 ||
+      c->act != (pool ? SSDK_ACT_RELU : SSDK_ACT_NONE) || c->res_mode || c->Cin != c->Cout || c->k != (pool ? 2 : 1) ||
+      c->stride != (pool ? 2 : 1) || (!pool && (c->scale || c->bias))) {
+    set_error("%s op: Cin=%d Cout=%d k=%d stride=%d groups=%d act=%d layouts %d/%d res_mode=%d (Cin = Cout, k = stride = %d, act %s, "
+              "NHWC in and out; w, residual, y2 and w_frag NULL%s)", what, c->Cin, c->Cout, c->k, c->stride, c->groups, c->act,
+              c->in_layout, c->out_layout, c->res_mode, pool ? 2 : 1, pool ? "relu" : "none", pool ? "" : "; scale and bias NULL");
+    return SSDK_E_BADARG;
+  }
+  if (pool) {
+    ssdk_dense_pool_desc d;
+    memset(&d, 0, sizeof(d));
+    d.x = c->x, d.y = c->y, d.a = c->scale, d.b = c->bias;
+    d.N = c->N, d.H = c->H, d.W = c->W, d.C = c->Cin, d.ld = c->split, d.dtype = c->dtype;
+    return ssdk_dense_pool(&d, st);
+  }
+  ssdk_dense_place_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x = c->x, d.y = c->y;
+  d.N = c->N, d.H = c->H, d.W = c->W, d.C = c->Cin, d.ld = c->split, d.dtype = c->dtype;
+  return ssdk_dense_place(&d, st);
+}
+
 extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* workspace, size_t workspace_bytes,
                                 void* stream) {
   if (int rc = ssdk::ctx_enter(ctx)) return rc;
@@ -1662,6 +1703,9 @@ extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* 
       else if ((ops[i].kind == SSDK_OP_CAT || ops[i].kind == SSDK_OP_SPP) && ops[i].lane == 0)
         rc = run_cat_op(&ops[i].conv, ops[i].kind == SSDK_OP_SPP, st);
       else if (ops[i].kind == SSDK_OP_DKRES && ops[i].lane == 0) rc = run_dkres_op(&ops[i].xpair, st);
+      else if (ops[i].kind == SSDK_OP_DENSE && ops[i].lane == 0) rc = run_dense_op(&ops[i].xpair, st);
+      else if ((ops[i].kind == SSDK_OP_DENSEPOOL || ops[i].kind == SSDK_OP_DENSEPLACE) && ops[i].lane == 0)
+        rc = run_dense_aux_op(&ops[i].conv, ops[i].kind == SSDK_OP_DENSEPOOL, st);
       else {
         set_error("unknown op kind %d", ops[i].kind);
         rc = SSDK_E_BADARG;

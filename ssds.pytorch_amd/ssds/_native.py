@@ -170,6 +170,7 @@ _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 U8 = _K["SSDK_U8"]  # ssdk_preprocess source only
 OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE, OP_CONVT, OP_CAT, OP_SPP, OP_DKRES = (
     _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE", "CONVT", "CAT", "SPP", "DKRES"))
+OP_DENSE, OP_DENSEPOOL, OP_DENSEPLACE = (_K["SSDK_OP_" + n] for n in ("DENSE", "DENSEPOOL", "DENSEPLACE"))
 MBSE_DW, MBSE_GATE, MBSE_PROJ = 1, 2, 4  # ssdk_mbse_desc.stages bits (0 = all three); the header has no names for them
 FUSE_SAME, FUSE_UP2, FUSE_POOL2 = _K["SSDK_FUSE_SAME"], _K["SSDK_FUSE_UP2"], _K["SSDK_FUSE_POOL2"]
 NCHW, NHWC = _K["SSDK_LAYOUT_NCHW"], _K["SSDK_LAYOUT_NHWC"]
@@ -216,6 +217,23 @@ DkresDesc = _HD.structs["ssdk_dkres_desc"]
 DkresDesc.__doc__ = "ssdk_dkres_desc: y = x + act2(bn2(conv3x3(act1(bn1(conv1x1(x)))))), the DarkNet residual block in one launch."
 DKRES_TILE_H, DKRES_TILE_W = _HD.constants["SSDK_DKRES_TILE_H"], _HD.constants["SSDK_DKRES_TILE_W"]  # a workgroup's output tile
 
+# include/ssdk_denselayer.h: the DenseNet dense layer as one launch, the front of a transition and the copy into a block's buffer
+DENSE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_denselayer.h")
+if not os.path.exists(DENSE_HEADER_PATH):
+    raise ImportError("include/ssdk_denselayer.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_dense_layer from it".format(
+        DENSE_HEADER_PATH))
+with open(DENSE_HEADER_PATH) as _f:
+    _HDN = parse_header(_f.read(), {"ssdk_dense_layer_desc": "DenseLayerDesc", "ssdk_dense_pool_desc": "DensePoolDesc",
+                                    "ssdk_dense_place_desc": "DensePlaceDesc"})
+DENSE_EXPORTS = tuple(_HDN.functions)
+DenseLayerDesc, DensePoolDesc, DensePlaceDesc = (_HDN.structs["ssdk_dense_%s_desc" % n] for n in ("layer", "pool", "place"))
+DenseLayerDesc.__doc__ = ("ssdk_dense_layer_desc: y[Cin : Cin + 32] = conv3x3(relu(bn2(conv1x1(relu(bn1(x[:Cin])))))) in one launch, x and y "
+                          "in one buffer of pixel stride ld.")
+DensePoolDesc.__doc__ = "ssdk_dense_pool_desc: y = avgpool2x2(relu(a * x + b)), x with pixel stride ld (the front of a DenseNet transition)."
+DensePlaceDesc.__doc__ = "ssdk_dense_place_desc: a dense NHWC tensor copied into channels [0, C) of a buffer with pixel stride ld."
+DENSE_TILE_H, DENSE_TILE_W = _HDN.constants["SSDK_DENSE_TILE_H"], _HDN.constants["SSDK_DENSE_TILE_W"]  # a workgroup's output tile
+DENSE_CMID, DENSE_COUT = _HDN.constants["SSDK_DENSE_CMID"], _HDN.constants["SSDK_DENSE_COUT"]
+
 # include/ssdk_cattrain.h: the same two operations of the YOLO TRAINING step, forward and backward on NCHW tensors (no descriptors)
 CATTRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_cattrain.h")
 if not os.path.exists(CATTRAIN_HEADER_PATH):
@@ -242,7 +260,7 @@ def _load():
     def bind(name):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions.get(name) or _HC.functions.get(name)
-                                   or _HD.functions.get(name) or _HCT.functions.get(name) or _HTT.functions[name])
+                                   or _HD.functions.get(name) or _HDN.functions.get(name) or _HCT.functions.get(name) or _HTT.functions[name])
         return fn
 
     # version FIRST: a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from the symbol lookup
@@ -254,12 +272,12 @@ def _load():
     if have < ABI_VERSION:
         raise ImportError("libssdk.so at {} is ABI {} but ssds/_native.py is written for ABI {}: rebuild it "
                           "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, have, ABI_VERSION))
-    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS + DKRES_EXPORTS + CATTRAIN_EXPORTS + CONVTTRAIN_EXPORTS:
+    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS + DKRES_EXPORTS + DENSE_EXPORTS + CATTRAIN_EXPORTS + CONVTTRAIN_EXPORTS:
         try:
             bind(name)
         except AttributeError:
             raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h (or ssdk_convt.h, ssdk_cat.h, ssdk_dkres.h, "
-                              "ssdk_cattrain.h, ssdk_convttrain.h next to it) declares: rebuild it "
+                              "ssdk_denselayer.h, ssdk_cattrain.h, ssdk_convttrain.h next to it) declares: rebuild it "
                               "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, name))
     # the ctypes mirrors must have the layout the library was BUILT with: a shorter struct would be read past its end.
     # SSDK_SIZEOF_X is the index of struct ssdk_x
@@ -276,9 +294,12 @@ def _load():
     mirrors = dict(_H.structs, **_HT.structs)
     mirrors.update(_HC.structs)
     mirrors.update(_HD.structs)
+    mirrors.update(_HDN.structs)
     for cname, fn in (("ssdk_augment_desc", lib.ssdk_augment_desc_bytes), ("ssdk_mbse_desc", lib.ssdk_mbse_desc_bytes),
                       ("ssdk_convt_desc", lib.ssdk_convt_desc_bytes), ("ssdk_cat_desc", lib.ssdk_cat_desc_bytes),
-                      ("ssdk_spp_desc", lib.ssdk_spp_desc_bytes), ("ssdk_dkres_desc", lib.ssdk_dkres_desc_bytes)):
+                      ("ssdk_spp_desc", lib.ssdk_spp_desc_bytes), ("ssdk_dkres_desc", lib.ssdk_dkres_desc_bytes),
+                      ("ssdk_dense_layer_desc", lib.ssdk_dense_layer_desc_bytes), ("ssdk_dense_pool_desc", lib.ssdk_dense_pool_desc_bytes),
+                      ("ssdk_dense_place_desc", lib.ssdk_dense_place_desc_bytes)):
         if int(fn()) != ctypes.sizeof(mirrors[cname]):
             raise ImportError("libssdk.so at {} has sizeof({}) = {} but ssds/_native.py mirrors it with {} bytes: "
                               "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, cname, int(fn()),

@@ -808,6 +808,136 @@ def dkres_native(x, p1, p2, y=None):
     return y
 
 
+# ---- DenseNet dense layer (csrc/ssdk_denselayer.hip): BN + ReLU -> 1x1 -> BN + ReLU -> 3x3 as one launch that reads channels [0, Cin)
+# of its block's buffer and writes [Cin, Cin + 32) -- no concatenation, the 128-channel middle map in LDS.
+def denselayer_enabled():
+    """SSDK_DENSELAYER (read whenever a plan is recorded): 0 sends a DenseNet backbone back to PyTorch-ROCm (docs/SWITCHES.md)."""
+    return os.environ.get("SSDK_DENSELAYER", "1") != "0"
+
+
+def fold_norm(bn):
+    """-> (a[C], b[C]) fp32 such that bn(x) == a * x + b in eval mode."""
+    var, mean = bn.running_var.detach().float(), bn.running_mean.detach().float()
+    gamma = bn.weight.detach().float() if bn.affine else torch.ones_like(var)
+    beta = bn.bias.detach().float() if bn.affine else torch.zeros_like(var)
+    a = gamma / torch.sqrt(var + bn.eps)
+    return a.contiguous(), (beta - mean * a).contiguous()
+
+
+class DenseLayerPack(object):
+    """One ``_DenseLayer`` (nets/densenet.py) packed for ``ssdk_dense_layer``: norm1 folded into the fp32 pair (a, b) that the
+    kernel applies to x on its way into the MFMA operand, norm2 folded into (scale1, bias1) behind the 1x1, both weight tensors
+    KRSC in 16 bits with their fragment-major images (``ssdk_weight_frag_bytes``; None with SSDK_WFRAG=0)."""
+
+    __slots__ = ("a", "b", "w1", "scale1", "bias1", "w2", "w1_frag", "w2_frag", "cin", "cmid", "cout")
+
+    @staticmethod
+    def unsupported(layer):
+        """None, or why ``layer`` is not the layer the kernel computes."""
+        c1, c2 = getattr(layer, "conv1", None), getattr(layer, "conv2", None)
+        n1, n2 = getattr(layer, "norm1", None), getattr(layer, "norm2", None)
+        if not (isinstance(c1, nn.Conv2d) and isinstance(c2, nn.Conv2d) and isinstance(n1, nn.BatchNorm2d) and isinstance(n2, nn.BatchNorm2d)
+                and isinstance(getattr(layer, "relu1", None), nn.ReLU) and isinstance(getattr(layer, "relu2", None), nn.ReLU)):
+            return "norm1, relu1, conv1, norm2, relu2, conv2 (BatchNorm2d, ReLU, Conv2d) expected"
+        if (c1.kernel_size != (1, 1) or c1.stride != (1, 1) or c1.padding != (0, 0) or c1.groups != 1 or c1.bias is not None
+                or c2.kernel_size != (3, 3) or c2.stride != (1, 1) or c2.padding != (1, 1) or c2.dilation != (1, 1) or c2.groups != 1
+                or c2.bias is not None or c2.in_channels != c1.out_channels or n1.num_features != c1.in_channels
+                or n2.num_features != c1.out_channels):
+            return "a bias-free 1x1 then a bias-free 3x3 / stride 1 / pad 1 expected"
+        if c1.out_channels != N.DENSE_CMID or c2.out_channels != N.DENSE_COUT:
+            return "bn_size * growth = {} middle and growth = {} output channels (the kernel has {} and {})".format(
+                c1.out_channels, c2.out_channels, N.DENSE_CMID, N.DENSE_COUT)
+        return None
+
+    def __init__(self, layer, dtype):
+        why = DenseLayerPack.unsupported(layer)
+        if why is not None:
+            raise N.SsdkError("dense layer: " + why)
+        self.cin, self.cmid, self.cout = layer.conv1.in_channels, layer.conv1.out_channels, layer.conv2.out_channels
+        self.a, self.b = fold_norm(layer.norm1)
+        self.scale1, self.bias1 = fold_norm(layer.norm2)
+        self.w1 = layer.conv1.weight.detach().float().reshape(self.cmid, self.cin).contiguous().to(dtype)
+        self.w2 = layer.conv2.weight.detach().float().permute(0, 2, 3, 1).contiguous().to(dtype)  # [32][3][3][128]
+        self.w1_frag = self.w2_frag = None
+        if USE_WFRAG:
+            self.w1_frag = _frag_image(self.w1, self.cmid, self.cin)
+            self.w2_frag = _frag_image(self.w2.reshape(self.cout, 9 * self.cmid), self.cout, 9 * self.cmid)
+
+
+def _frag_image(w2d, rows, k_elems):
+    """Fragment-major image of a [rows][K] matrix (ConvPack.frag's layout): [rows / 16][K / 32][4][16][8]."""
+    assert rows % 16 == 0 and k_elems % 32 == 0, (rows, k_elems)
+    img = w2d.view(rows // 16, 16, k_elems // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+    assert img.numel() * 2 == N.lib.ssdk_weight_frag_bytes(rows, k_elems)
+    return img
+
+
+def fill_dense_desc(d, x_ptr, n, h, w, cin, ld, pk, dtype_code, es=2):
+    """Fills an ``ssdk_dense_layer_desc`` -- or the ``ssdk_xpair_desc`` of an SSDK_OP_DENSE op (include/ssdk.h: scale2 / bias2 carry
+    (a, b), pad carries ld).  ``x_ptr``: channel 0 of pixel 0 of the block's buffer; y is ``cin`` channels behind it."""
+    assert cin == pk.cin, (cin, pk.cin)
+    d.x, d.y = x_ptr, x_ptr + cin * es
+    d.w1, d.scale1, d.bias1, d.w2 = pk.w1.data_ptr(), pk.scale1.data_ptr(), pk.bias1.data_ptr(), pk.w2.data_ptr()
+    d.w1_frag, d.w2_frag = (pk.w1_frag.data_ptr(), pk.w2_frag.data_ptr()) if pk.w1_frag is not None else (None, None)
+    d.N, d.H, d.W, d.Cin, d.dtype = n, h, w, cin, dtype_code
+    if isinstance(d, N.XpairDesc):
+        d.scale2, d.bias2, d.pad = pk.a.data_ptr(), pk.b.data_ptr(), ld
+        d.Cmid, d.Cout, d.act1, d.act2 = pk.cmid, pk.cout, N.ACT["relu"], N.ACT["none"]
+    else:
+        d.a, d.b, d.ld = pk.a.data_ptr(), pk.b.data_ptr(), ld
+    return d
+
+
+def _dense_buffer(buf, what):
+    """(n, h, w, ld) of a block buffer: a contiguous [N][H][W][ld] tensor in 16 bits on a HIP device."""
+    N.require_device(buf, what)
+    if buf.dim() != 4 or not buf.is_contiguous():
+        raise N.SsdkError("{}: the block buffer is a contiguous [N][H][W][ld] tensor, got {} with strides {}".format(
+            what, tuple(buf.shape), tuple(buf.stride())))
+    return tuple(int(v) for v in buf.shape)
+
+
+def dense_layer_native(buf, pk):
+    """One dense layer in place: reads ``buf[..., :pk.cin]`` and writes ``buf[..., pk.cin : pk.cin + 32]`` (``buf``: [N][H][W][ld])."""
+    n, h, w, ld = _dense_buffer(buf, "dense_layer")
+    d = fill_dense_desc(N.DenseLayerDesc(), buf.data_ptr(), n, h, w, pk.cin, ld, pk, N.dtype_code(buf))
+    with torch.cuda.device(buf.device):
+        rc = N.lib.ssdk_dense_layer(ctypes.byref(d), N.stream_ptr(buf.device))
+    N.check(rc, "dense_layer")
+    STATS["native_layers"] += 2
+    return buf
+
+
+def dense_pool_native(buf, c, a, b, y=None):
+    """avgpool2x2(relu(a * buf[..., :c] + b)) -> channels_last [N, c, H/2, W/2] (``y``: write there)."""
+    n, h, w, ld = _dense_buffer(buf, "dense_pool")
+    y = _out_tensor(y, (n, c, h // 2, w // 2), buf, torch.channels_last, "dense_pool")
+    d = N.DensePoolDesc()
+    d.x, d.y, d.a, d.b = buf.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr()
+    d.N, d.H, d.W, d.C, d.ld, d.dtype = n, h, w, c, ld, N.dtype_code(buf)
+    with torch.cuda.device(buf.device):
+        rc = N.lib.ssdk_dense_pool(ctypes.byref(d), N.stream_ptr(buf.device))
+    N.check(rc, "dense_pool")
+    STATS["native_layers"] += 1
+    return y
+
+
+def dense_place_native(x, buf):
+    """Copies channels_last ``x`` [N, C, H, W] into ``buf[..., :C]`` (``buf``: [N][H][W][ld]); the other channels stay."""
+    n, h, w, ld = _dense_buffer(buf, "dense_place")
+    x = _channels_last(x)
+    if tuple(x.shape) != (n, x.shape[1], h, w) or x.dtype != buf.dtype:
+        raise N.SsdkError("dense_place: x is {} {}, the buffer {} {}".format(tuple(x.shape), x.dtype, tuple(buf.shape), buf.dtype))
+    d = N.DensePlaceDesc()
+    d.x, d.y = x.data_ptr(), buf.data_ptr()
+    d.N, d.H, d.W, d.C, d.ld, d.dtype = n, h, w, int(x.shape[1]), ld, N.dtype_code(buf)
+    with torch.cuda.device(buf.device):
+        rc = N.lib.ssdk_dense_place(ctypes.byref(d), N.stream_ptr(buf.device))
+    N.check(rc, "dense_place")
+    STATS["native_layers"] += 1
+    return buf
+
+
 def fuse_native(a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_c=N.FUSE_SAME, y=None):
     """y = w0*a + w1*R_b(b) [+ w2*R_c(c)] (BiFPN weighted fusion, csrc/ssdk_fuse.hip); channels_last tensors (``y``: write
     there)."""
@@ -1130,6 +1260,36 @@ class ConvPlan(object):
         self.keep.extend([p1, p2])
         return (out, n, c, h, w)
 
+    def dense_block(self, n, ctot, h, w):
+        """The ONE buffer [n][h][w][ctot] of a dense block (csrc/ssdk_denselayer.hip): ``dense_place`` fills its first channels,
+        every ``dense`` op appends 32, and once the last layer is recorded ``(buffer, n, ctot, h, w)`` is an ordinary dense value
+        (pixel stride == channels).  It stays out of the arena's free list until that value is released."""
+        return self.arena.get(n * ctot * h * w * self.es)
+
+    def dense_place(self, val, block, ld):
+        """Copies the dense value ``val`` into channels [0, c) of ``block`` (pixel stride ``ld``); returns the channel count."""
+        buf, n, c, h, w = val
+        assert c % 8 == 0 and c <= ld and ld % 8 == 0, (c, ld)
+        self.layers.append(dict(kind="denseplace", x=buf, n=n, h=h, w=w, ch=c, ld=ld, y=block))
+        return c
+
+    def dense(self, block, n, cin, h, w, ld, pack):
+        """One dense layer as one op: reads channels [0, cin) of ``block`` and writes [cin, cin + 32); returns the new count."""
+        assert cin == pack.cin and cin + pack.cout <= ld, (cin, pack.cin, pack.cout, ld)
+        self.layers.append(dict(kind="dense", x=block, n=n, h=h, w=w, cin=cin, ld=ld, pack=pack, y=block))
+        self.keep.append(pack)
+        return cin + pack.cout
+
+    def dense_pool(self, val, a, b):
+        """The front of a transition on a finished block (``val``, pixel stride == channels): avgpool2x2(relu(a x + b)) as one op,
+        [n, c, h, w] -> [n, c, h / 2, w / 2] dense."""
+        buf, n, c, h, w = val
+        assert h >= 2 and w >= 2 and a.numel() == c == b.numel(), (c, h, w, a.numel())
+        out = self.arena.get(n * c * (h // 2) * (w // 2) * self.es)
+        self.layers.append(dict(kind="densepool", x=buf, n=n, h=h, w=w, ch=c, ld=c, a=a, b=b, y=out))
+        self.keep.extend([a, b])
+        return (out, n, c, h // 2, w // 2)
+
     def stem7(self, val, pack):
         buf, n, c, h, w = val
         ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
@@ -1259,6 +1419,24 @@ class ConvPlan(object):
                 fill_dkres_desc(op.xpair, self._ptr(L["x"], self.patches, i, "xpair.x"), self.arena.ptr(L["y"]), L["n"], L["h"],
                                 L["w"], L["pack"], L["pack2"], self.dtype_code)
                 continue
+            if kind == "dense":  # carried by the op's ssdk_xpair_desc (include/ssdk.h SSDK_OP_DENSE)
+                op.kind = N.OP_DENSE
+                fill_dense_desc(op.xpair, self.arena.ptr(L["x"]), L["n"], L["h"], L["w"], L["cin"], L["ld"], L["pack"], self.dtype_code,
+                                self.es)
+                continue
+            if kind in ("densepool", "denseplace"):  # carried by the op's ssdk_conv_desc (include/ssdk.h)
+                c = op.conv
+                c.x, c.y = self._ptr(L["x"], self.patches, i, "conv.x"), self.arena.ptr(L["y"])
+                c.N, c.Cin, c.H, c.W, c.Cout, c.groups = L["n"], L["ch"], L["h"], L["w"], L["ch"], 1
+                c.split, c.dtype, c.in_layout, c.out_layout = L["ld"], self.dtype_code, N.NHWC, N.NHWC
+                if kind == "densepool":
+                    op.kind = N.OP_DENSEPOOL
+                    c.scale, c.bias, c.k, c.stride, c.act = L["a"].data_ptr(), L["b"].data_ptr(), 2, 2, N.ACT["relu"]
+                else:
+                    op.kind = N.OP_DENSEPLACE
+                    c.k, c.stride, c.act = 1, 1, N.ACT["none"]
+                c.act2 = N.ACT["none"]
+                continue
             if kind == "stem7":
                 op.kind = N.OP_STEM7
                 st, pk = op.stem, L["pack"]
@@ -1334,7 +1512,23 @@ class ConvPlan(object):
                 rows.append(dict(name="spp %d k5,9,13 @%dx%d" % (ch, h, w), flops=0.0, bytes=float(es * n * h * w * 5 * ch),
                                  kind="fuse"))
                 continue
+            if L.get("kind") == "densepool":  # the block's c channels in, a quarter of the pixels out
+                n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
+                rows.append(dict(name="densepool %d @%dx%d" % (ch, h, w), flops=16.0 * n * ch * (h // 2) * (w // 2),
+                                 bytes=float(es * n * ch * (h * w + (h // 2) * (w // 2)) + 8 * ch), kind="pool"))
+                continue
+            if L.get("kind") == "denseplace":  # data movement: the map in and out once
+                n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
+                rows.append(dict(name="denseplace %d>%d @%dx%d" % (ch, L["ld"], h, w), flops=0.0, bytes=float(es * 2 * n * ch * h * w),
+                                 kind="fuse"))
+                continue
             pk, n, h, w = L["pack"], L["n"], L["h"], L["w"]
+            if L.get("kind") == "dense":  # both convolutions' MACs; Cin channels in, 32 out (m never leaves the CU), the weights
+                macs = n * h * w * (pk.cin * pk.cmid + 9 * pk.cmid * pk.cout)
+                byt = es * (n * h * w * (pk.cin + pk.cout) + pk.cin * pk.cmid + 9 * pk.cmid * pk.cout)
+                rows.append(dict(name="dense %d>%d>%d k1,k3 @%dx%d" % (pk.cin, pk.cmid, pk.cout, h, w), flops=2.0 * macs,
+                                 bytes=float(byt), kind="conv"))
+                continue
             if L.get("kind") == "mbse":  # depthwise + SE + gated projection: x in, y out, t written and read once, the weights
                 ho, wo = _out_hw(h, w, pk.k, pk.stride)
                 macs = n * (ho * wo * pk.k * pk.k * pk.cin + 2 * pk.cin * pk.r + ho * wo * pk.cin * pk.cout)

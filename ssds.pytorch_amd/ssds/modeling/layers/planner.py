@@ -11,8 +11,9 @@ import torch.nn as nn
 
 import os
 
-from .fused_conv import (ConvPack, ConvPlan, ConvTPack, MbPack, MbSePack, StemPack, cat_supported, conv_kind, dkres_supported, pack_heads,
-                         sequential_groups, xpair_supported)
+from .fused_conv import (ConvPack, ConvPlan, ConvTPack, DenseLayerPack, MbPack, MbSePack, StemPack, cat_supported, conv_kind,
+                         denselayer_enabled, dkres_supported, fold_norm, pack_heads, sequential_groups, xpair_supported)
+from ssds import _native as N
 
 
 class PlanUnsupported(Exception):
@@ -347,10 +348,99 @@ def record_darknet(plan, val, net):
     return outputs
 
 
+def record_densenet(plan, val, net):
+    """DenseNet (nets/densenet.py): the stem on the 7x7 stem kernel + max-pool, then per dense block ONE buffer [n][h][w][Ctot] --
+    ``place`` copies the block's input into its first channels and each dense layer is one ``dense`` op (csrc/ssdk_denselayer.hip)
+    that reads channels [0, Cin) and writes [Cin, Cin + 32): no concatenation is recorded.  A transition pools FIRST
+    (``densepool``: BN + ReLU + 2x2 average) and runs its bias-free 1x1 behind that, on a quarter of the pixels -- the same
+    function in real arithmetic, since the convolution is linear.  A finished block's buffer IS the backbone map."""
+    from ssds.modeling.nets.densenet import DenseNet, _DenseBlock, _DenseLayer, _Transition
+
+    if not isinstance(net, DenseNet):
+        raise PlanUnsupported("backbone {} has no planner".format(type(net).__name__))
+    if not denselayer_enabled():
+        raise PlanUnsupported("SSDK_DENSELAYER=0: the DenseNet backbone runs on PyTorch-ROCm")
+    dt = plan.dtype
+    stem = dict(net.conv1.named_children())
+    if (list(stem) != ["conv", "norm", "relu", "pool"] or not isinstance(stem["conv"], nn.Conv2d)
+            or not isinstance(stem["norm"], nn.BatchNorm2d) or not StemPack.supported(stem["conv"], stem["norm"])
+            or stem["conv"].bias is not None or not isinstance(stem["relu"], nn.ReLU) or not isinstance(stem["pool"], nn.MaxPool2d)
+            or _pair(stem["pool"].kernel_size) != (3, 3) or _pair(stem["pool"].stride) != (2, 2) or _pair(stem["pool"].padding) != (1, 1)
+            or stem["pool"].ceil_mode):
+        raise PlanUnsupported("DenseNet conv1: 7x7 / stride 2 conv + BatchNorm + ReLU + 3x3 / stride 2 max-pool expected")
+    cur = plan.stem7(val, StemPack(stem["conv"], stem["norm"], "relu", dt))
+    pooled = plan.pool(cur)
+    plan.release(cur)
+    cur = pooled
+    outputs = []
+    for level in range(1, len(net.block_config) + 1):
+        if level > max(net.outputs):
+            break
+        if level > 1:
+            what = "transition{}".format(level - 1)
+            tr = getattr(net, what)
+            parts = dict(tr.named_children())
+            if not isinstance(tr, _Transition) or list(parts) != ["norm", "relu", "conv", "pool"]:
+                raise PlanUnsupported("DenseNet {}: block {} has no planner".format(what, type(tr).__name__))
+            conv, pool = parts["conv"], parts["pool"]
+            if (not isinstance(parts["norm"], nn.BatchNorm2d) or not isinstance(parts["relu"], nn.ReLU) or not isinstance(conv, nn.Conv2d)
+                    or conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.groups != 1 or conv.bias is not None
+                    or not isinstance(pool, nn.AvgPool2d) or _pair(pool.kernel_size) != (2, 2) or _pair(pool.stride) != (2, 2)
+                    or _pair(pool.padding) != (0, 0) or pool.ceil_mode or parts["norm"].num_features != cur[2] or cur[2] % 8):
+                raise PlanUnsupported("DenseNet {}: BatchNorm + ReLU + bias-free 1x1 + AvgPool2d(2, 2) expected".format(what))
+            if cur[3] < 2 or cur[4] < 2:
+                raise PlanUnsupported("DenseNet {}: a {} x {} map has no 2x2 window".format(what, cur[3], cur[4]))
+            a, b = fold_norm(parts["norm"])
+            pooled = plan.dense_pool(cur, a, b)
+            if not any(cur is o for o in outputs):
+                plan.release(cur)
+            cur = plan.conv(pooled, ConvPack(conv, None, "none", dt))  # (linear and bias-free: it commutes with the average)
+            plan.release(pooled)
+        what = "denseblock{}".format(level)
+        block = getattr(net, what)
+        if not isinstance(block, _DenseBlock):
+            raise PlanUnsupported("DenseNet {}: block {} has no planner".format(what, type(block).__name__))
+        _, n, c0, h, w = cur
+        layers = list(block.items())
+        ctot = c0 + N.DENSE_COUT * len(layers)
+        packs = []
+        for j, (lname, layer) in enumerate(layers):
+            lwhat = "{}.{}".format(what, lname)
+            if not isinstance(layer, _DenseLayer):
+                raise PlanUnsupported("DenseNet {}: block {} has no planner".format(lwhat, type(layer).__name__))
+            why = DenseLayerPack.unsupported(layer)
+            if why is not None:
+                raise PlanUnsupported("DenseNet {}: {}".format(lwhat, why))
+            if layer.drop_rate > 0 and layer.training:
+                raise PlanUnsupported("DenseNet {}: drop_rate {} in training mode".format(lwhat, layer.drop_rate))
+            cin = c0 + N.DENSE_COUT * j
+            if layer.conv1.in_channels != cin:
+                raise PlanUnsupported("DenseNet {}: {} input channels where the block has {}".format(lwhat, layer.conv1.in_channels, cin))
+            if not N.lib.ssdk_dense_layer_supported(cin, h, w, ctot, plan.dtype_code):
+                raise PlanUnsupported("DenseNet {}: ssdk_dense_layer_supported refuses Cin={} on {}x{} with pixel stride {}".format(
+                    lwhat, cin, h, w, ctot))
+            packs.append(DenseLayerPack(layer, dt))
+        buf = plan.dense_block(n, ctot, h, w)
+        c = plan.dense_place(cur, buf, ctot)
+        plan.release(cur)
+        for pk in packs:
+            c = plan.dense(buf, n, c, h, w, ctot, pk)
+        assert c == ctot, (c, ctot)
+        cur = (buf, n, ctot, h, w)
+        if level in net.outputs:
+            outputs.append(cur)
+    return outputs
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
 def record_backbone(plan, val, net):
-    """Backbone maps of a planned backbone (MobileNet, ResNet, RegNetX, EfficientNet, DarkNet) from the image value;
+    """Backbone maps of a planned backbone (MobileNet, ResNet, RegNetX, EfficientNet, DarkNet, DenseNet) from the image value;
     PlanUnsupported otherwise."""
     from ssds.modeling.nets.darknet import DarkNet
+    from ssds.modeling.nets.densenet import DenseNet
     from ssds.modeling.nets.efficientnet import EfficientEx
     from ssds.modeling.nets.mobilenet import MobileNetEx
     from ssds.modeling.nets.regnet import RegNet
@@ -366,6 +456,8 @@ def record_backbone(plan, val, net):
         return record_regnet(plan, val, net)
     if isinstance(net, DarkNet):
         return record_darknet(plan, val, net)
+    if isinstance(net, DenseNet):
+        return record_densenet(plan, val, net)
     raise PlanUnsupported("backbone {} has no planner".format(type(net).__name__))
 
 
