@@ -945,13 +945,28 @@ size_t ssdk_mbse_desc_bytes(void);
  *            Cin = Cout = C, k = stride = 2, act SSDK_ACT_RELU
  *     PLACE  x dense [N][H][W][C]; y buffer of pixel stride `split` (= ld), channels [0, C); Cin = Cout = C, k = stride = 1,
  *            act SSDK_ACT_NONE, scale and bias NULL
- *     in_layout = out_layout = SSDK_LAYOUT_NHWC, groups <= 1, res_mode 0; w, residual, y2 and w_frag NULL. */
+ *     in_layout = out_layout = SSDK_LAYOUT_NHWC, groups <= 1, res_mode 0; w, residual, y2 and w_frag NULL.
+ *
+ * SSDK_OP_SHUFFLE / SSDK_OP_SHUFFLEDOWN (executor op kinds 14, 15, lane 0 only): the ShuffleNetV2 unit as one launch, stride 1 and
+ * stride 2 -- ssdk_shuffle_unit / ssdk_shuffle_down of include/ssdk_shuffle.h.  They bring no member to ssdk_op either.
+ *   `mb` carries x, y and the three weight sets of branch2, read as
+ *     w_expand, scale_expand, bias_expand     w1 (fragment-major image), scale1, bias1
+ *     w_dw                                    wd [9][P]
+ *     bias_dw                                 fp32 [2][P]: scale2, then bias2 (the member is the only one the depthwise has)
+ *     w_project, scale_project, bias_project  w3 (image), scale3, bias3
+ *     Chid = Cb, Cout = 2 Cb; SHUFFLE: Cin = Cout, stride 1; SHUFFLEDOWN: Cin = the input's real channels, stride 2
+ *     residual = stem = variant = 0, w_image NULL (anything else: SSDK_E_BADARG); N, H, W, dtype as in ssdk_shuffle_unit_desc
+ *   SHUFFLEDOWN: `xpair` carries the two weight sets of branch1, read as
+ *     w1, scale1, bias1             b1_wd [9][KP], b1_scale1, b1_bias1 (the depthwise; act1 = SSDK_ACT_NONE)
+ *     w2_frag, scale2, bias2        b1_w2 (image), b1_scale2, b1_bias2 (act2 = SSDK_ACT_RELU); w2 NULL
+ *     Cin = Cmid = the unit's Cin, Cout = Cb; pad = ld_in (the input's pixel stride in channels, 0: 8 ceil(Cin / 8)); x, y unused. */
 enum { SSDK_OP_CONV = 0, SSDK_OP_MBCONV = 1, SSDK_OP_FUSE = 2, SSDK_OP_STEM7 = 3, SSDK_OP_POOL = 4, SSDK_OP_XPAIR = 5,
        SSDK_OP_MBSE = 6 /* lane 0 only */, SSDK_OP_CONVT = 7 /* lane 0 only; described by `conv`, see above */,
        SSDK_OP_CAT = 8, SSDK_OP_SPP = 9 /* both lane 0 only; described by `conv`, see above */,
        SSDK_OP_DKRES = 10 /* lane 0 only; described by `xpair`, see above */,
        SSDK_OP_DENSE = 11 /* lane 0 only; described by `xpair`, see above */,
-       SSDK_OP_DENSEPOOL = 12, SSDK_OP_DENSEPLACE = 13 /* both lane 0 only; described by `conv`, see above */ };
+       SSDK_OP_DENSEPOOL = 12, SSDK_OP_DENSEPLACE = 13 /* both lane 0 only; described by `conv`, see above */,
+       SSDK_OP_SHUFFLE = 14, SSDK_OP_SHUFFLEDOWN = 15 /* both lane 0 only; described by `mb` (and `xpair`), see above */ };
 typedef struct ssdk_op {
   int32_t kind, lane;
   ssdk_conv_desc conv;

@@ -30,6 +30,7 @@
 #include "../../include/ssdk_cat.h"
 #include "../../include/ssdk_dkres.h"
 #include "../../include/ssdk_denselayer.h"
+#include "../../include/ssdk_shuffle.h"
 
 namespace ssdk {
 
@@ -1595,6 +1596,46 @@ static int run_dense_aux_op(const ssdk_conv_desc* c, bool pool, hipStream_t st) 
   return ssdk_dense_place(&d, st);
 }
 
+// SSDK_OP_SHUFFLE / SSDK_OP_SHUFFLEDOWN: the op's ssdk_mbconv_desc read as branch2 of a ShuffleNetV2 unit and, for the stride-2 unit,
+// its ssdk_xpair_desc as branch1 (include/ssdk.h) -> ssdk_shuffle_unit / ssdk_shuffle_down
+static int run_shuffle_op(const ssdk_op* op, bool down, hipStream_t st) {
+  const ssdk_mbconv_desc* m = &op->mb;
+  const ssdk_xpair_desc* b = &op->xpair;
+  const char* what = down ? "shuffledown" : "shuffle";
+  if (m->stride != (down ? 2 : 1) || m->Cout != 2 * m->Chid || (!down && m->Cin != m->Cout) || m->residual || m->stem || m->variant ||
+      m->w_image || !m->bias_dw) {
+    set_error("%s op: Cin=%d Chid=%d Cout=%d stride=%d residual=%d stem=%d variant=%d (stride %d, Cout = 2 Chid%s; no residual, stem, "
+              "variant or image; bias_dw = fp32 [2][P] scale then bias)", what, m->Cin, m->Chid, m->Cout, m->stride, m->residual, m->stem,
+              m->variant, down ? 2 : 1, down ? "" : " = Cin");
+    return SSDK_E_BADARG;
+  }
+  const int P = (m->Chid + SSDK_SHUFFLE_CHUNK - 1) / SSDK_SHUFFLE_CHUNK * SSDK_SHUFFLE_CHUNK;
+  const float* affine = (const float*)m->bias_dw;
+  if (!down) {
+    ssdk_shuffle_unit_desc d;
+    memset(&d, 0, sizeof(d));
+    d.x = m->x, d.y = m->y, d.w1 = m->w_expand, d.scale1 = m->scale_expand, d.bias1 = m->bias_expand;
+    d.wd = m->w_dw, d.scale2 = affine, d.bias2 = affine + P;
+    d.w3 = m->w_project, d.scale3 = m->scale_project, d.bias3 = m->bias_project;
+    d.N = m->N, d.H = m->H, d.W = m->W, d.Cb = m->Chid, d.dtype = m->dtype;
+    return ssdk_shuffle_unit(&d, st);
+  }
+  if (b->Cin != m->Cin || b->Cmid != m->Cin || b->Cout != m->Chid || b->act1 != SSDK_ACT_NONE || b->act2 != SSDK_ACT_RELU || b->w2) {
+    set_error("shuffledown op: branch1 Cin=%d Cmid=%d Cout=%d act1=%d act2=%d (Cin = Cmid = the unit's Cin, Cout = Chid, act1 none, act2 "
+              "relu, w2 NULL: the 1x1 comes as w2_frag)", b->Cin, b->Cmid, b->Cout, b->act1, b->act2);
+    return SSDK_E_BADARG;
+  }
+  ssdk_shuffle_down_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x = m->x, d.y = m->y;
+  d.b1_wd = b->w1, d.b1_scale1 = b->scale1, d.b1_bias1 = b->bias1, d.b1_w2 = b->w2_frag, d.b1_scale2 = b->scale2, d.b1_bias2 = b->bias2;
+  d.w1 = m->w_expand, d.scale1 = m->scale_expand, d.bias1 = m->bias_expand;
+  d.wd = m->w_dw, d.scale2 = affine, d.bias2 = affine + P;
+  d.w3 = m->w_project, d.scale3 = m->scale_project, d.bias3 = m->bias_project;
+  d.N = m->N, d.H = m->H, d.W = m->W, d.Cin = m->Cin, d.ld_in = b->pad, d.Cb = m->Chid, d.dtype = m->dtype;
+  return ssdk_shuffle_down(&d, st);
+}
+
 extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* workspace, size_t workspace_bytes,
                                 void* stream) {
   if (int rc = ssdk::ctx_enter(ctx)) return rc;
@@ -1706,6 +1747,8 @@ extern "C" int ssdk_run_ops_ctx(ssdk_ctx* ctx, const ssdk_op* ops, int n, void* 
       else if (ops[i].kind == SSDK_OP_DENSE && ops[i].lane == 0) rc = run_dense_op(&ops[i].xpair, st);
       else if ((ops[i].kind == SSDK_OP_DENSEPOOL || ops[i].kind == SSDK_OP_DENSEPLACE) && ops[i].lane == 0)
         rc = run_dense_aux_op(&ops[i].conv, ops[i].kind == SSDK_OP_DENSEPOOL, st);
+      else if ((ops[i].kind == SSDK_OP_SHUFFLE || ops[i].kind == SSDK_OP_SHUFFLEDOWN) && ops[i].lane == 0)
+        rc = run_shuffle_op(&ops[i], ops[i].kind == SSDK_OP_SHUFFLEDOWN, st);
       else {
         set_error("unknown op kind %d", ops[i].kind);
         rc = SSDK_E_BADARG;

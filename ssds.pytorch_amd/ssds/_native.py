@@ -171,6 +171,7 @@ U8 = _K["SSDK_U8"]  # ssdk_preprocess source only
 OP_CONV, OP_MBCONV, OP_FUSE, OP_STEM7, OP_POOL, OP_XPAIR, OP_MBSE, OP_CONVT, OP_CAT, OP_SPP, OP_DKRES = (
     _K["SSDK_OP_" + n] for n in ("CONV", "MBCONV", "FUSE", "STEM7", "POOL", "XPAIR", "MBSE", "CONVT", "CAT", "SPP", "DKRES"))
 OP_DENSE, OP_DENSEPOOL, OP_DENSEPLACE = (_K["SSDK_OP_" + n] for n in ("DENSE", "DENSEPOOL", "DENSEPLACE"))
+OP_SHUFFLE, OP_SHUFFLEDOWN = _K["SSDK_OP_SHUFFLE"], _K["SSDK_OP_SHUFFLEDOWN"]
 MBSE_DW, MBSE_GATE, MBSE_PROJ = 1, 2, 4  # ssdk_mbse_desc.stages bits (0 = all three); the header has no names for them
 FUSE_SAME, FUSE_UP2, FUSE_POOL2 = _K["SSDK_FUSE_SAME"], _K["SSDK_FUSE_UP2"], _K["SSDK_FUSE_POOL2"]
 NCHW, NHWC = _K["SSDK_LAYOUT_NCHW"], _K["SSDK_LAYOUT_NHWC"]
@@ -234,6 +235,22 @@ DensePlaceDesc.__doc__ = "ssdk_dense_place_desc: a dense NHWC tensor copied into
 DENSE_TILE_H, DENSE_TILE_W = _HDN.constants["SSDK_DENSE_TILE_H"], _HDN.constants["SSDK_DENSE_TILE_W"]  # a workgroup's output tile
 DENSE_CMID, DENSE_COUT = _HDN.constants["SSDK_DENSE_CMID"], _HDN.constants["SSDK_DENSE_COUT"]
 
+# include/ssdk_shuffle.h: the ShuffleNetV2 unit as one launch, stride 1 and stride 2
+SHUFFLE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_shuffle.h")
+if not os.path.exists(SHUFFLE_HEADER_PATH):
+    raise ImportError("include/ssdk_shuffle.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_shuffle_unit from it".format(
+        SHUFFLE_HEADER_PATH))
+with open(SHUFFLE_HEADER_PATH) as _f:
+    _HSF = parse_header(_f.read(), {"ssdk_shuffle_unit_desc": "ShuffleUnitDesc", "ssdk_shuffle_down_desc": "ShuffleDownDesc"})
+SHUFFLE_EXPORTS = tuple(_HSF.functions)
+ShuffleUnitDesc, ShuffleDownDesc = _HSF.structs["ssdk_shuffle_unit_desc"], _HSF.structs["ssdk_shuffle_down_desc"]
+ShuffleUnitDesc.__doc__ = ("ssdk_shuffle_unit_desc: y[2i] = x[i], y[2i + 1] = branch2(x[Cb:])[i] -- the stride-1 ShuffleNetV2 unit in one "
+                           "launch, the channel shuffle in the store.")
+ShuffleDownDesc.__doc__ = "ssdk_shuffle_down_desc: y[2i] = branch1(x)[i], y[2i + 1] = branch2(x)[i] -- the stride-2 unit in one launch."
+SHUFFLE_TILE_H, SHUFFLE_TILE_W = _HSF.constants["SSDK_SHUFFLE_TILE_H"], _HSF.constants["SSDK_SHUFFLE_TILE_W"]  # a workgroup's output tile
+SHUFFLE_DOWN_TILE_H, SHUFFLE_DOWN_TILE_W = _HSF.constants["SSDK_SHUFFLE_DOWN_TILE_H"], _HSF.constants["SSDK_SHUFFLE_DOWN_TILE_W"]
+SHUFFLE_CHUNK = _HSF.constants["SSDK_SHUFFLE_CHUNK"]  # weight images and vectors are zero-padded to a multiple of it
+
 # include/ssdk_cattrain.h: the same two operations of the YOLO TRAINING step, forward and backward on NCHW tensors (no descriptors)
 CATTRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_cattrain.h")
 if not os.path.exists(CATTRAIN_HEADER_PATH):
@@ -260,7 +277,7 @@ def _load():
     def bind(name):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions.get(name) or _HC.functions.get(name)
-                                   or _HD.functions.get(name) or _HDN.functions.get(name) or _HCT.functions.get(name) or _HTT.functions[name])
+                                   or _HD.functions.get(name) or _HDN.functions.get(name) or _HSF.functions.get(name) or _HCT.functions.get(name) or _HTT.functions[name])
         return fn
 
     # version FIRST: a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from the symbol lookup
@@ -272,12 +289,12 @@ def _load():
     if have < ABI_VERSION:
         raise ImportError("libssdk.so at {} is ABI {} but ssds/_native.py is written for ABI {}: rebuild it "
                           "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, have, ABI_VERSION))
-    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS + DKRES_EXPORTS + DENSE_EXPORTS + CATTRAIN_EXPORTS + CONVTTRAIN_EXPORTS:
+    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS + DKRES_EXPORTS + DENSE_EXPORTS + SHUFFLE_EXPORTS + CATTRAIN_EXPORTS + CONVTTRAIN_EXPORTS:
         try:
             bind(name)
         except AttributeError:
             raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h (or ssdk_convt.h, ssdk_cat.h, ssdk_dkres.h, "
-                              "ssdk_denselayer.h, ssdk_cattrain.h, ssdk_convttrain.h next to it) declares: rebuild it "
+                              "ssdk_denselayer.h, ssdk_shuffle.h, ssdk_cattrain.h, ssdk_convttrain.h next to it) declares: rebuild it "
                               "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, name))
     # the ctypes mirrors must have the layout the library was BUILT with: a shorter struct would be read past its end.
     # SSDK_SIZEOF_X is the index of struct ssdk_x
@@ -295,11 +312,14 @@ def _load():
     mirrors.update(_HC.structs)
     mirrors.update(_HD.structs)
     mirrors.update(_HDN.structs)
+    mirrors.update(_HSF.structs)
     for cname, fn in (("ssdk_augment_desc", lib.ssdk_augment_desc_bytes), ("ssdk_mbse_desc", lib.ssdk_mbse_desc_bytes),
                       ("ssdk_convt_desc", lib.ssdk_convt_desc_bytes), ("ssdk_cat_desc", lib.ssdk_cat_desc_bytes),
                       ("ssdk_spp_desc", lib.ssdk_spp_desc_bytes), ("ssdk_dkres_desc", lib.ssdk_dkres_desc_bytes),
                       ("ssdk_dense_layer_desc", lib.ssdk_dense_layer_desc_bytes), ("ssdk_dense_pool_desc", lib.ssdk_dense_pool_desc_bytes),
-                      ("ssdk_dense_place_desc", lib.ssdk_dense_place_desc_bytes)):
+                      ("ssdk_dense_place_desc", lib.ssdk_dense_place_desc_bytes),
+                      ("ssdk_shuffle_unit_desc", lib.ssdk_shuffle_unit_desc_bytes),
+                      ("ssdk_shuffle_down_desc", lib.ssdk_shuffle_down_desc_bytes)):
         if int(fn()) != ctypes.sizeof(mirrors[cname]):
             raise ImportError("libssdk.so at {} has sizeof({}) = {} but ssds/_native.py mirrors it with {} bytes: "
                               "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, cname, int(fn()),

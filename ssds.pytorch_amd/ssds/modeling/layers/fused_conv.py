@@ -14,7 +14,9 @@ Switch: ``SSDK_FUSED_CONV`` = "1" (default: HIP kernels in eval mode on a HIP de
 everywhere; for A/B measurements only, never chosen silently).
 """
 import ctypes
+import contextlib
 import os
+import threading
 
 import torch
 import torch.nn as nn
@@ -65,6 +67,86 @@ USE_GCONV_ANY = os.environ.get("SSDK_GCONV_ANY", "1") != "0"
 GCONV_ANY_MAX_WIDTH = 256  # channels per group (csrc/ssdk_gconv_any.hip launch_gconv3x3_any)
 
 
+class _PaddedMaps(threading.local):
+    on = False
+    depth = 0
+
+
+_PADDED_MAPS = _PaddedMaps()
+
+
+@contextlib.contextmanager
+def padded_maps_scope():
+    """The recording of ONE plan.  Inside it ``allow_padded_maps()`` -- called by a backbone recorder that produced a map whose
+    channel count is no multiple of 8 (ShuffleNetV2: 116 -> 120, 244 -> 248 channels per pixel, zeros in the padding) -- lets
+    ``conv_kind`` take the dense convolutions that read such a map: their packs zero-pad their input channels (``ConvPack.in_segs``).
+    Outside a scope nothing changes: a module-path layer on a real 116-channel tensor stays 'not covered'."""
+    before = _PADDED_MAPS.on
+    _PADDED_MAPS.on = False
+    _PADDED_MAPS.depth += 1
+    try:
+        yield
+    finally:
+        _PADDED_MAPS.depth -= 1
+        _PADDED_MAPS.on = before
+
+
+def allow_padded_maps():
+    """For the rest of the enclosing ``padded_maps_scope`` (an error outside one: the switch would never be turned off)."""
+    if _PADDED_MAPS.depth == 0:
+        raise N.SsdkError("allow_padded_maps() outside padded_maps_scope()")
+    _PADDED_MAPS.on = True
+
+
+def in_padded_maps_scope():
+    return _PADDED_MAPS.depth > 0
+
+
+def pad8(c):
+    return (c + 7) // 8 * 8
+
+
+class PaddedValue(tuple):
+    """A plan value ``(buffer, n, c, h, w)`` whose ``c`` PHYSICAL channels per pixel hold fewer real ones: ``segs`` = ((real,
+    physical), ...) in channel order, zeros in every gap (one segment for a backbone map, several behind a concatenation)."""
+
+    def __new__(cls, val, segs):
+        self = super(PaddedValue, cls).__new__(cls, val)
+        self.segs = tuple((int(r), int(q)) for r, q in segs)
+        assert sum(q for _, q in self.segs) == val[2], (self.segs, val[2])
+        return self
+
+    @property
+    def real_channels(self):
+        return sum(r for r, _ in self.segs)
+
+
+def value_segs(val):
+    """((real, physical), ...) of a plan value; a plain value is one segment without padding."""
+    return getattr(val, "segs", ((val[2], val[2]),))
+
+
+def _pad_cols(w, segs):
+    """[..., sum real] -> [..., sum physical]: zero columns behind every segment's real ones."""
+    parts, at = [], 0
+    for real, phys in segs:
+        parts.append(w[..., at:at + real])
+        at += real
+        if phys > real:
+            parts.append(w.new_zeros(tuple(w.shape[:-1]) + (phys - real,)))
+    assert at == w.shape[-1], (segs, tuple(w.shape))
+    return torch.cat(parts, -1).contiguous()
+
+
+def _strip_cols(w, segs):
+    parts, at = [], 0
+    for real, phys in segs:
+        parts.append(w[..., at:at + real])
+        at += phys
+    assert at == w.shape[-1], (segs, tuple(w.shape))
+    return torch.cat(parts, -1).contiguous()
+
+
 def conv_kind(conv):
     """'dense' | 'dw' | 'g16' | 'gany' | 'stem' | None (None: not covered by the HIP kernels -> torch, reported)."""
     k = conv.kernel_size
@@ -74,8 +156,11 @@ def conv_kind(conv):
         return None
     if conv.groups == 1:
         if conv.in_channels <= 4:
-            return "stem" if (k[0] == 3 and conv.out_channels in (16, 32, 64)) else None
-        return "dense" if conv.in_channels % 8 == 0 else None
+            # (24, inside padded_maps_scope: ShuffleNetV2's conv1, packed with its output rows zero-padded to 32 -- the stem kernel's
+            #  widths are 16, 32, 64)
+            return "stem" if (k[0] == 3 and (conv.out_channels in (16, 32, 64) or (conv.out_channels == 24 and _PADDED_MAPS.on))) else None
+        # a channel count that is no multiple of 8 only inside a plan whose backbone hands out zero-padded maps (padded_maps_scope)
+        return "dense" if conv.in_channels % 8 == 0 or _PADDED_MAPS.on else None
     if conv.groups == conv.in_channels == conv.out_channels and k[0] == 3 and conv.in_channels % 8 == 0:
         return "dw"
     if conv.in_channels == conv.out_channels == conv.groups * 16 and k[0] == 3:
@@ -124,7 +209,43 @@ USE_WFRAG = os.environ.get("SSDK_WFRAG", "1") != "0"
 class ConvPack(object):
     """Weights of one fused layer in kernel layout (built once per model/dtype)."""
 
-    __slots__ = ("kind", "w", "scale", "bias", "cin", "cout", "k", "stride", "groups", "act", "_frag")
+    __slots__ = ("kind", "w", "scale", "bias", "cin", "cout", "k", "stride", "groups", "act", "_frag", "in_segs", "cout_real")
+
+    def with_input_segs(self, segs):
+        """A copy of this dense pack for an input laid out as ``segs`` = ((real, physical), ...): zero weight columns at every
+        padding channel, so whatever the padding holds contributes nothing (and a produced map's padding IS zeros)."""
+        segs = tuple((int(r), int(q)) for r, q in segs)
+        if self.kind != "dense":
+            raise N.SsdkError("a {} layer cannot read a zero-padded map".format(self.kind))
+        real = _strip_cols(self.w, self.in_segs) if self.in_segs is not None else self.w
+        if sum(r for r, _ in segs) != real.shape[-1]:
+            raise N.SsdkError("a layer of {} input channels cannot read a map of {} real channels".format(
+                real.shape[-1], sum(r for r, _ in segs)))
+        other = ConvPack.__new__(ConvPack)
+        for name in ConvPack.__slots__:
+            setattr(other, name, getattr(self, name))
+        other._frag = None
+        other.in_segs = segs if any(r != q for r, q in segs) else None
+        other.w = _pad_cols(real, segs)
+        other.cin = sum(q for _, q in segs)
+        return other
+
+    def with_padded_output(self):
+        """A copy of this dense pack that writes pad8(cout) channels per pixel: zero weight rows, zero scale and bias behind the real
+        ones, so the padding channels of the map it produces are act(0) = 0 (act none | relu | relu6 | silu)."""
+        if self.kind != "dense":
+            raise N.SsdkError("a {} layer cannot write a zero-padded map".format(self.kind))
+        other = ConvPack.__new__(ConvPack)
+        for name in ConvPack.__slots__:
+            setattr(other, name, getattr(self, name))
+        other._frag = None
+        extra = pad8(self.cout) - self.cout
+        other.w = torch.cat([self.w, self.w.new_zeros((extra,) + tuple(self.w.shape[1:]))], 0).contiguous()
+        other.bias = torch.cat([self.bias, self.bias.new_zeros(extra)]).contiguous()
+        if self.scale is not None:
+            other.scale = torch.cat([self.scale, self.scale.new_zeros(extra)]).contiguous()
+        other.cout = pad8(self.cout)
+        return other
 
     def frag(self):
         """Fragment-major image of the dense weights (include/ssdk.h ``ssdk_weight_frag_bytes``) for the kernels that stream
@@ -161,6 +282,8 @@ class ConvPack(object):
 
     def __init__(self, conv, bn, act, dtype, extra_cout=None):
         self._frag = None
+        self.in_segs = None
+        self.cout_real = conv.out_channels
         self.kind = conv_kind(conv)
         if self.kind is None:
             raise N.SsdkError("conv {} is not covered by the HIP kernels".format(conv))
@@ -171,11 +294,20 @@ class ConvPack(object):
         if self.kind == "stem":  # fp32 weights with the BN scale folded in, KRSC
             self.w = (w * scale.view(-1, 1, 1, 1)).permute(0, 2, 3, 1).contiguous()
             self.scale = None
+            if self.cout not in (16, 32, 64):  # zero output rows up to the stem kernel's next width: relu(0) = 0 in the padding
+                wide = min(c for c in (16, 32, 64) if c >= self.cout)
+                self.w = torch.cat([self.w, self.w.new_zeros((wide - self.cout,) + tuple(self.w.shape[1:]))], 0).contiguous()
+                bias = torch.cat([bias, bias.new_zeros(wide - self.cout)]).contiguous()
+                self.cout = wide
         elif self.kind == "dw":  # [C,1,3,3] -> [3][3][C]
             self.w = w[:, 0].permute(1, 2, 0).contiguous().to(dtype)
             self.scale = scale
         else:  # [Cout,Cin,kh,kw] -> [Cout][kh][kw][Cin]
             self.w = w.permute(0, 2, 3, 1).contiguous().to(dtype)
+            if self.kind == "dense" and self.cin % 8:  # reads a zero-padded map (conv_kind: only inside padded_maps_scope)
+                self.in_segs = ((self.cin, pad8(self.cin)),)
+                self.w = _pad_cols(self.w, self.in_segs)
+                self.cin = pad8(self.cin)
             # (the grouped kernels have no scale-free form: a layer without BatchNorm passes fold_bn's vector of ones)
             self.scale = scale if bn is not None or self.kind in ("g16", "gany") else None
         self.bias = bias
@@ -938,6 +1070,237 @@ def dense_place_native(x, buf):
     return buf
 
 
+# ---- ShuffleNetV2 unit (csrc/ssdk_shuffle.hip): chunk / branch2 (/ branch1) / cat / channel shuffle as one launch that reads x once
+# and writes the interleaved y once.  Tensors are dense NHWC [N][H][W][Cp], Cp = pad8(C): padding channels are never read and are
+# written as zeros.
+def shuffleunit_enabled():
+    """SSDK_SHUFFLEUNIT (read whenever a plan is recorded): 0 sends a ShuffleNetV2 backbone back to PyTorch-ROCm (docs/SWITCHES.md)."""
+    return os.environ.get("SSDK_SHUFFLEUNIT", SHUFFLEUNIT_DEFAULT) != "0"
+
+
+SHUFFLEUNIT_DEFAULT = "1"  # DESIGN 4.5l: the plan's slowest forward beats the module path's fastest on both configs
+
+
+def shuffle_pad(cb):
+    """Width the weight images and vectors of a branch of ``cb`` channels are zero-padded to (include/ssdk_shuffle.h)."""
+    return (cb + N.SHUFFLE_CHUNK - 1) // N.SHUFFLE_CHUNK * N.SHUFFLE_CHUNK
+
+
+def _zero_padded(t, shape):
+    out = t.new_zeros(shape)
+    out[tuple(slice(0, d) for d in t.shape)] = t
+    return out.contiguous()
+
+
+def _shuffle_pw(conv, rows, cols, dtype):
+    """1x1 conv -> (zero-padded [rows][cols] matrix in ``dtype``, its fragment-major image)."""
+    w = conv.weight.detach().float().reshape(conv.out_channels, conv.in_channels).to(dtype)
+    w = _zero_padded(w, (rows, cols))
+    return w, _frag_image(w, rows, cols)
+
+
+def _shuffle_dw(conv, cols, dtype):
+    """depthwise 3x3 [C, 1, 3, 3] -> [9 taps][cols] in ``dtype``, zeros behind the C real channels."""
+    w = conv.weight.detach().float()[:, 0].permute(1, 2, 0).reshape(9, conv.out_channels).to(dtype)
+    return _zero_padded(w, (9, cols))
+
+
+def _shuffle_affine(bn, cols):
+    """-> fp32 [2][cols]: the folded scale, then the folded bias, zeros in the padding (one tensor: an executor op has ONE member
+    for the depthwise's constants, include/ssdk.h SSDK_OP_SHUFFLE)."""
+    a, b = fold_norm(bn)
+    return _zero_padded(torch.stack([a, b]), (2, cols))
+
+
+def _branch_why(seq, kinds, what):
+    mods = list(seq.children())
+    if len(mods) != len(kinds) or not all(isinstance(m, k) for m, k in zip(mods, kinds)):
+        return "{}: {} expected, got {}".format(what, ", ".join(k.__name__ for k in kinds), ", ".join(type(m).__name__ for m in mods))
+    return None
+
+
+def _pw_why(conv, cin, cout, what):
+    if (conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) or conv.groups != 1 or conv.bias is not None
+            or conv.in_channels != cin or conv.out_channels != cout):
+        return "{}: a bias-free 1x1 {} -> {} expected, got {}".format(what, cin, cout, conv)
+    return None
+
+
+def _dw_why(conv, c, stride, what):
+    if (conv.kernel_size != (3, 3) or conv.stride != (stride, stride) or conv.padding != (1, 1) or conv.dilation != (1, 1)
+            or conv.groups != c or conv.in_channels != c or conv.out_channels != c or conv.bias is not None
+            or conv.padding_mode != "zeros"):
+        return "{}: a bias-free depthwise 3x3 / stride {} / pad 1 on {} channels expected, got {}".format(what, stride, c, conv)
+    return None
+
+
+_BRANCH2 = (nn.Conv2d, nn.BatchNorm2d, nn.ReLU, nn.Conv2d, nn.BatchNorm2d, nn.Conv2d, nn.BatchNorm2d, nn.ReLU)
+_BRANCH1 = (nn.Conv2d, nn.BatchNorm2d, nn.Conv2d, nn.BatchNorm2d, nn.ReLU)
+
+
+def _shuffle_unit_why(unit, stride):
+    b1, b2 = getattr(unit, "branch1", None), getattr(unit, "branch2", None)
+    if not isinstance(b1, nn.Sequential) or not isinstance(b2, nn.Sequential) or getattr(unit, "stride", None) != stride:
+        return "a stride-{} unit with branch1 and branch2 (Sequential) expected, got {}".format(stride, type(unit).__name__)
+    why = _branch_why(b2, _BRANCH2, "branch2")
+    if why:
+        return why
+    cb = b2[5].out_channels
+    cin = b2[0].in_channels
+    if stride == 1:
+        if len(b1) != 0:
+            return "branch1 of a stride-1 unit is empty"
+        if cin != cb:
+            return "branch2 of a stride-1 unit maps Cb -> Cb, got {} -> {}".format(cin, cb)
+    else:
+        why = (_branch_why(b1, _BRANCH1, "branch1") or _dw_why(b1[0], cin, 2, "branch1.0") or _pw_why(b1[2], cin, cb, "branch1.2"))
+        if why:
+            return why
+        if b1[1].num_features != cin or b1[3].num_features != cb:
+            return "branch1: BatchNorm widths {} / {} for {} -> {} channels".format(b1[1].num_features, b1[3].num_features, cin, cb)
+    why = _pw_why(b2[0], cin, cb, "branch2.0") or _dw_why(b2[3], cb, stride, "branch2.3") or _pw_why(b2[5], cb, cb, "branch2.5")
+    if why:
+        return why
+    if any(b2[i].num_features != cb for i in (1, 4, 6)):
+        return "branch2: a BatchNorm that is not {} wide".format(cb)
+    return None
+
+
+class ShuffleUnitPack(object):
+    """One stride-1 ``InvertedResidual`` (nets/shufflenet.py) packed for ``ssdk_shuffle_unit``: branch2's three weight sets, every
+    BatchNorm folded into an fp32 (scale, bias) pair that the kernel applies in fp32; 16-bit weights, zero-padded to
+    ``p = shuffle_pad(cb)`` rows and K columns (``w1`` / ``w3``: the padded matrices, ``w1_img`` / ``w3_img``: their fragment-major
+    images, which are what the kernel reads); ``affine2`` = fp32 [2][p], ``scale2`` / ``bias2`` its rows."""
+
+    __slots__ = ("cb", "p", "w1", "w1_img", "scale1", "bias1", "wd", "affine2", "scale2", "bias2", "w3", "w3_img", "scale3", "bias3")
+    stride = 1
+
+    @staticmethod
+    def unsupported(unit):
+        """None, or why ``unit`` is not the unit the kernel computes."""
+        why = _shuffle_unit_why(unit, 1)
+        if why is None and not N.lib.ssdk_shuffle_unit_supported(unit.branch2[5].out_channels, 1, 1, N.BF16):
+            why = "ssdk_shuffle_unit_supported refuses Cb = {}".format(unit.branch2[5].out_channels)
+        return why
+
+    def __init__(self, unit, dtype):
+        why = type(self).unsupported(unit)
+        if why is not None:
+            raise N.SsdkError("shuffle unit: " + why)
+        self._pack_branch2(unit.branch2, dtype)
+
+    def _pack_branch2(self, b2, dtype, kp=None):
+        self.cb = b2[5].out_channels
+        self.p = shuffle_pad(self.cb)
+        self.w1, self.w1_img = _shuffle_pw(b2[0], self.p, self.p if kp is None else kp, dtype)
+        self.scale1, self.bias1 = _shuffle_affine(b2[1], self.p)
+        self.wd = _shuffle_dw(b2[3], self.p, dtype)
+        self.affine2 = _shuffle_affine(b2[4], self.p)
+        self.scale2, self.bias2 = self.affine2[0], self.affine2[1]
+        self.w3, self.w3_img = _shuffle_pw(b2[5], self.p, self.p, dtype)
+        self.scale3, self.bias3 = _shuffle_affine(b2[6], self.p)
+
+
+class ShuffleDownPack(ShuffleUnitPack):
+    """One stride-2 ``InvertedResidual`` packed for ``ssdk_shuffle_down``: branch2 as in ``ShuffleUnitPack`` (its first 1x1 reads
+    all ``cin`` input channels: K padded to ``kp`` = 32 ceil(cin / 32)) plus branch1's depthwise (``b1_wd`` [9][kp], ``b1_scale1`` /
+    ``b1_bias1`` fp32 [kp]) and 1x1 (``b1_w2`` [p][kp] with its image, ``b1_scale2`` / ``b1_bias2`` fp32 [p])."""
+
+    __slots__ = ("cin", "kp", "b1_wd", "b1_scale1", "b1_bias1", "b1_w2", "b1_w2_img", "b1_scale2", "b1_bias2")
+    stride = 2
+
+    @staticmethod
+    def unsupported(unit):
+        why = _shuffle_unit_why(unit, 2)
+        if why is None and not N.lib.ssdk_shuffle_down_supported(unit.branch2[0].in_channels, unit.branch2[5].out_channels, 1, 1, N.BF16):
+            why = "ssdk_shuffle_down_supported refuses Cin = {}, Cb = {}".format(unit.branch2[0].in_channels,
+                                                                                unit.branch2[5].out_channels)
+        return why
+
+    def __init__(self, unit, dtype):
+        why = type(self).unsupported(unit)
+        if why is not None:
+            raise N.SsdkError("shuffle unit: " + why)
+        self.cin = unit.branch2[0].in_channels
+        self.kp = (self.cin + 31) // 32 * 32
+        self._pack_branch2(unit.branch2, dtype, kp=self.kp)
+        b1 = unit.branch1
+        self.b1_wd = _shuffle_dw(b1[0], self.kp, dtype)
+        self.b1_scale1, self.b1_bias1 = _shuffle_affine(b1[1], self.kp)
+        self.b1_w2, self.b1_w2_img = _shuffle_pw(b1[2], self.p, self.kp, dtype)
+        self.b1_scale2, self.b1_bias2 = _shuffle_affine(b1[3], self.p)
+
+
+def fill_shuffle_desc(d, x_ptr, y_ptr, n, h, w, pk, dtype_code, ld_in=0):
+    """Fills an ``ssdk_shuffle_unit_desc`` / ``ssdk_shuffle_down_desc`` -- or the ``mb`` (+ ``xpair``) members of an executor op
+    (include/ssdk.h SSDK_OP_SHUFFLE / SSDK_OP_SHUFFLEDOWN) -- from a ``ShuffleUnitPack`` / ``ShuffleDownPack``."""
+    down = pk.stride == 2
+    if isinstance(d, N.Op):
+        m = d.mb
+        m.x, m.y = x_ptr, y_ptr
+        m.w_expand, m.scale_expand, m.bias_expand = pk.w1_img.data_ptr(), pk.scale1.data_ptr(), pk.bias1.data_ptr()
+        m.w_dw, m.bias_dw = pk.wd.data_ptr(), pk.affine2.data_ptr()
+        m.w_project, m.scale_project, m.bias_project = pk.w3_img.data_ptr(), pk.scale3.data_ptr(), pk.bias3.data_ptr()
+        m.N, m.H, m.W, m.Chid, m.Cout, m.stride, m.dtype = n, h, w, pk.cb, 2 * pk.cb, pk.stride, dtype_code
+        m.Cin = pk.cin if down else 2 * pk.cb
+        if down:
+            b = d.xpair
+            b.w1, b.scale1, b.bias1 = pk.b1_wd.data_ptr(), pk.b1_scale1.data_ptr(), pk.b1_bias1.data_ptr()
+            b.w2_frag, b.scale2, b.bias2 = pk.b1_w2_img.data_ptr(), pk.b1_scale2.data_ptr(), pk.b1_bias2.data_ptr()
+            b.Cin, b.Cmid, b.Cout, b.act1, b.act2, b.pad, b.dtype = pk.cin, pk.cin, pk.cb, N.ACT["none"], N.ACT["relu"], ld_in, dtype_code
+            b.N, b.H, b.W = n, h, w
+        return d
+    d.x, d.y = x_ptr, y_ptr
+    d.w1, d.scale1, d.bias1 = pk.w1_img.data_ptr(), pk.scale1.data_ptr(), pk.bias1.data_ptr()
+    d.wd, d.scale2, d.bias2 = pk.wd.data_ptr(), pk.scale2.data_ptr(), pk.bias2.data_ptr()
+    d.w3, d.scale3, d.bias3 = pk.w3_img.data_ptr(), pk.scale3.data_ptr(), pk.bias3.data_ptr()
+    d.N, d.H, d.W, d.Cb, d.dtype = n, h, w, pk.cb, dtype_code
+    if down:
+        d.b1_wd, d.b1_scale1, d.b1_bias1 = pk.b1_wd.data_ptr(), pk.b1_scale1.data_ptr(), pk.b1_bias1.data_ptr()
+        d.b1_w2, d.b1_scale2, d.b1_bias2 = pk.b1_w2_img.data_ptr(), pk.b1_scale2.data_ptr(), pk.b1_bias2.data_ptr()
+        d.Cin, d.ld_in = pk.cin, ld_in
+    return d
+
+
+def _nhwc(x, what):
+    """(n, h, w, c) of a dense NHWC tensor [N][H][W][C] in 16 bits on a HIP device."""
+    N.require_device(x, what)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise N.SsdkError("{}: a contiguous [N][H][W][C] tensor expected, got {} with strides {}".format(
+            what, tuple(x.shape), tuple(x.stride())))
+    return tuple(int(v) for v in x.shape)
+
+
+def shuffle_unit_native(x, pk, y=None):
+    """One stride-1 unit: ``x`` [N][H][W][Cp], Cp = pad8(2 cb), of which channels [0, 2 cb) are read -> ``y`` of the same shape, zeros
+    in [2 cb, Cp) (``y``: write there)."""
+    n, h, w, c = _nhwc(x, "shuffle_unit")
+    if c != pad8(2 * pk.cb):
+        raise N.SsdkError("shuffle_unit: x has {} channels per pixel, a unit of Cb = {} reads {}".format(c, pk.cb, pad8(2 * pk.cb)))
+    y = _out_tensor(y, (n, h, w, c), x, torch.contiguous_format, "shuffle_unit")
+    d = fill_shuffle_desc(N.ShuffleUnitDesc(), x.data_ptr(), y.data_ptr(), n, h, w, pk, N.dtype_code(x))
+    with torch.cuda.device(x.device):
+        rc = N.lib.ssdk_shuffle_unit(ctypes.byref(d), N.stream_ptr(x.device))
+    N.check(rc, "shuffle_unit")
+    STATS["native_layers"] += 3
+    return y
+
+
+def shuffle_down_native(x, pk, y=None):
+    """One stride-2 unit: ``x`` [N][H][W][ld], ld a multiple of 8 and >= cin, of which channels [0, cin) are read -> ``y``
+    [N][Ho][Wo][pad8(2 cb)], Ho = (H - 1) / 2 + 1 (``y``: write there)."""
+    n, h, w, ld = _nhwc(x, "shuffle_down")
+    if ld < pk.cin or ld % 8:
+        raise N.SsdkError("shuffle_down: x has {} channels per pixel, a unit of Cin = {} needs a multiple of 8 >= Cin".format(ld, pk.cin))
+    y = _out_tensor(y, (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, pad8(2 * pk.cb)), x, torch.contiguous_format, "shuffle_down")
+    d = fill_shuffle_desc(N.ShuffleDownDesc(), x.data_ptr(), y.data_ptr(), n, h, w, pk, N.dtype_code(x), ld_in=ld)
+    with torch.cuda.device(x.device):
+        rc = N.lib.ssdk_shuffle_down(ctypes.byref(d), N.stream_ptr(x.device))
+    N.check(rc, "shuffle_down")
+    STATS["native_layers"] += 5
+    return y
+
+
 def fuse_native(a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_c=N.FUSE_SAME, y=None):
     """y = w0*a + w1*R_b(b) [+ w2*R_c(c)] (BiFPN weighted fusion, csrc/ssdk_fuse.hip); channels_last tensors (``y``: write
     there)."""
@@ -1160,7 +1523,15 @@ class ConvPlan(object):
         levels, planner._record_extras_and_towers; include/ssdk.h: lane 2 = the in-line kernel choice): its input and
         output buffers are pinned like a side-lane head's."""
         buf, n, c, h, w = val
+        pack = self._fit(val, pack)
         assert c == pack.cin, (c, pack.cin)
+        if pack.cout % 8 and _PADDED_MAPS.on:  # (behind a backbone of zero-padded maps) an NHWC map of e.g. 244 channels: written as 248
+            # per pixel, zeros in the padding
+            if (pack.act if act is None else act) not in ("none", "relu", "relu6", "silu"):
+                raise N.SsdkError("a zero-padded map behind the activation {}".format(pack.act if act is None else act))
+            pack = pack.with_padded_output()
+        if residual is not None:
+            assert value_segs(residual) == ((getattr(pack, "cout_real", pack.cout), pack.cout),), (value_segs(residual), pack.cout)
         ho, wo = _out_hw(h, w, pack.k, pack.stride)
         out = self.arena.get(n * pack.cout * ho * wo * self.es)
         if lane:
@@ -1172,7 +1543,7 @@ class ConvPlan(object):
                                 res=residual[0] if residual is not None else None, res_mode=res_mode, nchw=False,
                                 role=role, lane=lane))
         self.keep.append(pack)
-        return (out, n, pack.cout, ho, wo)
+        return self._padded((out, n, pack.cout, ho, wo), getattr(pack, "cout_real", pack.cout))
 
     def mbconv(self, val, pk):
         buf, n, c, h, w = val
@@ -1225,7 +1596,10 @@ class ConvPlan(object):
         assert cat_supported(c1, c2, h, w, up2) is None, cat_supported(c1, c2, h, w, up2)
         out = self.arena.get(n * (c1 + c2) * h * w * self.es)
         self.layers.append(dict(kind="cat", x=buf, b=bbuf, n=n, h=h, w=w, c1=c1, c2=c2, up2=bool(up2), y=out))
-        return (out, n, c1 + c2, h, w)
+        val = (out, n, c1 + c2, h, w)
+        if hasattr(a, "segs") or hasattr(b, "segs"):  # zero-padded maps keep their padding where it is: the readers' packs follow
+            val = PaddedValue(val, value_segs(a) + value_segs(b))
+        return val
 
     def spp(self, val):
         """The SPP block ``x || maxpool5(x) || maxpool9(x) || maxpool13(x)`` as one op (csrc/ssdk_cat.hip):
@@ -1234,10 +1608,13 @@ class ConvPlan(object):
         assert c >= 8 and c % 8 == 0, c
         out = self.arena.get(n * 4 * c * h * w * self.es)
         self.layers.append(dict(kind="spp", x=buf, n=n, h=h, w=w, ch=c, y=out))
+        if hasattr(val, "segs"):  # (max-pooling keeps the zeros of a padded map where they are, in each of the four slices)
+            return PaddedValue((out, n, 4 * c, h, w), val.segs * 4)
         return (out, n, 4 * c, h, w)
 
     def xpair(self, val, p1, p2, lane=0):
         buf, n, c, h, w = val
+        p1 = self._fit(val, p1)
         assert c == p1.cin, (c, p1.cin)
         ho, wo = _out_hw(h, w, 3, 2)
         out = self.arena.get(n * p2.cout * ho * wo * self.es)
@@ -1290,6 +1667,48 @@ class ConvPlan(object):
         self.keep.extend([a, b])
         return (out, n, c, h // 2, w // 2)
 
+    def shuffle_unit(self, val, pack):
+        """A stride-1 ShuffleNetV2 unit as one op (csrc/ssdk_shuffle.hip): [n, Cp, h, w] -> [n, Cp, h, w], Cp = pad8(2 cb) physical
+        channels of which 2 cb are real (a ``PaddedValue`` when they differ).  The output is a buffer of its own."""
+        buf, n, c, h, w = val
+        assert c == pad8(2 * pack.cb) and value_segs(val)[0][0] == 2 * pack.cb, (c, value_segs(val), pack.cb)
+        out = self.arena.get(n * c * h * w * self.es)
+        self.layers.append(dict(kind="shuffle", x=buf, n=n, h=h, w=w, pack=pack, y=out))
+        self.keep.append(pack)
+        return self._padded((out, n, c, h, w), 2 * pack.cb)
+
+    def shuffle_down(self, val, pack):
+        """A stride-2 unit as one op: [n, ld, h, w] of which the first ``pack.cin`` channels are real -> [n, pad8(2 cb), ho, wo]."""
+        buf, n, c, h, w = val
+        assert c % 8 == 0 and c >= pack.cin and value_segs(val)[0][0] == pack.cin, (c, value_segs(val), pack.cin)
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        cp = pad8(2 * pack.cb)
+        out = self.arena.get(n * cp * ho * wo * self.es)
+        self.layers.append(dict(kind="shuffledown", x=buf, n=n, h=h, w=w, ld=c, pack=pack, y=out))
+        self.keep.append(pack)
+        return self._padded((out, n, cp, ho, wo), 2 * pack.cb)
+
+    @staticmethod
+    def _padded(val, real):
+        return PaddedValue(val, ((real, val[2]),)) if real != val[2] else val
+
+    def _fit(self, val, pack):
+        """``pack`` for reading ``val``: as it is, or -- when ``val`` is a zero-padded map laid out differently from what the pack was
+        built for (behind a concatenation) -- a copy with zero weight columns at ``val``'s padding channels."""
+        segs = getattr(val, "segs", None)
+        if segs is not None and getattr(pack, "in_segs", None) != segs:
+            pack = pack.with_input_segs(segs)
+        return pack
+
+    def read(self, val):
+        """The REAL channels of a recorded value after a run, as a channels_last view [n, c, h, w] of its arena buffer (a zero-padded
+        map of one segment is sliced to its real channels)."""
+        buf, n, c, h, w = val
+        t = self.arena.bufs[buf][0][: n * c * h * w * self.es].view(self.dtype).view(n, h, w, c)
+        segs = value_segs(val)
+        assert len(segs) == 1, segs
+        return t[..., :segs[0][0]].permute(0, 3, 1, 2)
+
     def stem7(self, val, pack):
         buf, n, c, h, w = val
         ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
@@ -1311,6 +1730,9 @@ class ConvPlan(object):
         out = self.arena.get(n * ch * h * w * self.es)
         self.layers.append(dict(kind="fuse", a=a, b=b, c=c, w=tuple(float(v) for v in weights), mode_b=mode_b,
                                 mode_c=mode_c, n=n, h=h, w_=w, ch=ch, y=out))
+        if hasattr(a, "segs"):  # (a weighted sum of maps padded alike is padded alike)
+            assert all(value_segs(v) == a.segs for v in (b, c) if v is not None), [value_segs(v) for v in (a, b, c) if v is not None]
+            return PaddedValue((out, n, ch, h, w), a.segs)
         return (out, n, ch, h, w)
 
     def head(self, val, pack, split=None, act="none", act2=None, tag="both", lane=None, position=None, level=None):
@@ -1318,6 +1740,8 @@ class ConvPlan(object):
         conv of one shared tower (``tag='loc' | 'conf'``).  ``level``: the pyramid level of the output when the heads are
         recorded out of level order (small levels first, on the side stream); the outputs are returned in level order."""
         buf, n, c, h, w = val
+        pack = self._fit(val, pack)
+        assert c == pack.cin, (c, pack.cin)
         ho, wo = _out_hw(h, w, pack.k, pack.stride)
         # small heads are leaves of latency-bound work: they run on the executor's side stream next to the main
         # chain (SSDK_SIDE_STREAM); the big levels fill the chip on their own and stay in line.  A side-lane op
@@ -1418,6 +1842,11 @@ class ConvPlan(object):
                 op.kind = N.OP_DKRES
                 fill_dkres_desc(op.xpair, self._ptr(L["x"], self.patches, i, "xpair.x"), self.arena.ptr(L["y"]), L["n"], L["h"],
                                 L["w"], L["pack"], L["pack2"], self.dtype_code)
+                continue
+            if kind in ("shuffle", "shuffledown"):  # carried by the op's mb (+ xpair) members (include/ssdk.h SSDK_OP_SHUFFLE)
+                op.kind = N.OP_SHUFFLE if kind == "shuffle" else N.OP_SHUFFLEDOWN
+                fill_shuffle_desc(op, self._ptr(L["x"], self.patches, i, "mb.x"), self.arena.ptr(L["y"]), L["n"], L["h"], L["w"],
+                                  L["pack"], self.dtype_code, ld_in=L.get("ld", 0))
                 continue
             if kind == "dense":  # carried by the op's ssdk_xpair_desc (include/ssdk.h SSDK_OP_DENSE)
                 op.kind = N.OP_DENSE
@@ -1528,6 +1957,19 @@ class ConvPlan(object):
                 byt = es * (n * h * w * (pk.cin + pk.cout) + pk.cin * pk.cmid + 9 * pk.cmid * pk.cout)
                 rows.append(dict(name="dense %d>%d>%d k1,k3 @%dx%d" % (pk.cin, pk.cmid, pk.cout, h, w), flops=2.0 * macs,
                                  bytes=float(byt), kind="conv"))
+                continue
+            if L.get("kind") == "shuffle":  # branch2's MACs; x in and y out once (neither intermediate leaves the CU), the weights
+                cb = pk.cb
+                rows.append(dict(name="shuffle %d k1,dw3,k1 @%dx%d" % (2 * cb, h, w), flops=2.0 * n * h * w * (2 * cb * cb + 9 * cb),
+                                 bytes=float(es * (n * h * w * 4 * cb + 2 * cb * cb + 9 * cb)), kind="conv"))
+                continue
+            if L.get("kind") == "shuffledown":  # both branches' MACs; x in once, y out once, the weights
+                cb, cin = pk.cb, pk.cin
+                ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+                macs = n * (h * w * cin * cb + ho * wo * (9 * cb + cb * cb + 9 * cin + cin * cb))
+                rows.append(dict(name="shuffledown %d>%d k1,dw3s2,k1 @%dx%d" % (cin, 2 * cb, h, w), flops=2.0 * macs,
+                                 bytes=float(es * (n * (h * w * cin + ho * wo * 2 * cb) + 2 * cin * cb + cb * cb + 9 * (cin + cb))),
+                                 kind="conv"))
                 continue
             if L.get("kind") == "mbse":  # depthwise + SE + gated projection: x in, y out, t written and read once, the weights
                 ho, wo = _out_hw(h, w, pk.k, pk.stride)

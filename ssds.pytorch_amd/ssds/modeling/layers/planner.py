@@ -11,13 +11,26 @@ import torch.nn as nn
 
 import os
 
-from .fused_conv import (ConvPack, ConvPlan, ConvTPack, DenseLayerPack, MbPack, MbSePack, StemPack, cat_supported, conv_kind,
-                         denselayer_enabled, dkres_supported, fold_norm, pack_heads, sequential_groups, xpair_supported)
+import functools
+
+from .fused_conv import (ConvPack, ConvPlan, ConvTPack, DenseLayerPack, MbPack, MbSePack, ShuffleDownPack, ShuffleUnitPack, StemPack,
+                         allow_padded_maps, cat_supported, conv_kind, denselayer_enabled, dkres_supported, fold_norm, in_padded_maps_scope, pack_heads,
+                         padded_maps_scope, sequential_groups, shuffleunit_enabled, value_segs, xpair_supported)
 from ssds import _native as N
 
 
 class PlanUnsupported(Exception):
     pass
+
+
+def _one_recording(build):
+    """A plan builder runs inside ``fused_conv.padded_maps_scope``: a backbone that hands out zero-padded maps (ShuffleNetV2) lets the
+    dense convolutions behind it read them, for this recording only."""
+    @functools.wraps(build)
+    def wrapped(*a, **kw):
+        with padded_maps_scope():
+            return build(*a, **kw)
+    return wrapped
 
 
 def flatten(module):
@@ -113,6 +126,7 @@ def record_mobilenet(plan, val, net, on_output=None):
     return outputs
 
 
+@_one_recording
 def build_ssd_plan(model, x):
     """SSD (ssds/ssd.py) on a planned backbone (MobileNet, ResNet) -> finalized ConvPlan for inputs shaped like ``x``."""
     plan = ConvPlan(x.device, x.dtype, x.shape)
@@ -432,13 +446,88 @@ def record_densenet(plan, val, net):
     return outputs
 
 
+def record_shufflenet(plan, val, net):
+    """``_record_shufflenet`` inside the plan builder's ``padded_maps_scope`` (the neck behind it reads the padded maps), or inside
+    one of its own when the backbone is recorded alone."""
+    if in_padded_maps_scope():
+        return _record_shufflenet(plan, val, net)
+    with padded_maps_scope():
+        return _record_shufflenet(plan, val, net)
+
+
+def _record_shufflenet(plan, val, net):
+    """ShuffleNetV2 (nets/shufflenet.py): conv1 on the stem kernel (its 24 output channels as 32 channels per pixel, zeros in the
+    padding), the 3x3 / 2 max-pool, then ONE op per unit (csrc/ssdk_shuffle.hip): ``shuffledown`` for the first unit of a stage,
+    ``shuffle`` for the others.  No chunk, concatenation or channel shuffle is recorded: the interleave is the store of the unit's
+    kernel.  A stage's map has pad8(C) channels per pixel, zeros in [C, pad8(C)) (``fused_conv.PaddedValue`` when C % 8 != 0: 116 ->
+    120, 244 -> 248); the packs of the convolutions that read it zero-pad their input channels (``ConvPack.in_segs``)."""
+    from ssds.modeling.nets.shufflenet import InvertedResidual, ShuffleNetV2
+
+    if not isinstance(net, ShuffleNetV2):
+        raise PlanUnsupported("backbone {} has no planner".format(type(net).__name__))
+    if not shuffleunit_enabled():
+        raise PlanUnsupported("SSDK_SHUFFLEUNIT=0: the ShuffleNetV2 backbone runs on PyTorch-ROCm")
+    allow_padded_maps()
+    dt = plan.dtype
+    pool = net.maxpool
+    if (not isinstance(pool, nn.MaxPool2d) or _pair(pool.kernel_size) != (3, 3) or _pair(pool.stride) != (2, 2)
+            or _pair(pool.padding) != (1, 1) or _pair(pool.dilation) != (1, 1) or pool.ceil_mode):
+        raise PlanUnsupported("ShuffleNetV2 maxpool: a 3x3 / stride 2 / pad 1 max-pool expected, got {}".format(pool))
+    try:
+        groups = groups_of(net.conv1)
+    except PlanUnsupported as e:
+        raise PlanUnsupported("ShuffleNetV2 conv1: {}".format(e))
+    if len(groups) != 1 or conv_kind(groups[0][0]) != "stem" or groups[0][0].stride != (2, 2) or groups[0][2] != "relu":
+        raise PlanUnsupported("ShuffleNetV2 conv1: a 3x3 / stride 2 conv on the image + BatchNorm + ReLU expected")
+    c_real = groups[0][0].out_channels
+    cur = record_chain(plan, val, net.conv1, keep_input=True)  # the image is not an arena buffer
+    pooled = plan.pool(cur)
+    plan.release(cur)
+    cur = plan._padded(pooled, c_real)
+    outputs = []
+    for level in (2, 3, 4):
+        if level > max(net.outputs):
+            break
+        what = "stage{}".format(level)
+        stage = getattr(net, what, None)
+        if not isinstance(stage, nn.Sequential) or len(stage) == 0:
+            raise PlanUnsupported("ShuffleNetV2 {}: a Sequential of units expected, got {}".format(what, type(stage).__name__))
+        for j, unit in enumerate(stage):
+            uwhat = "{}.{}".format(what, j)
+            if not isinstance(unit, InvertedResidual):
+                raise PlanUnsupported("ShuffleNetV2 {}: block {} has no planner".format(uwhat, type(unit).__name__))
+            cls = ShuffleDownPack if unit.stride == 2 else ShuffleUnitPack
+            why = cls.unsupported(unit)
+            if why is not None:
+                raise PlanUnsupported("ShuffleNetV2 {}: {}".format(uwhat, why))
+            _, n, c, h, w = cur
+            real = value_segs(cur)[0][0]
+            cin = unit.branch2[0].in_channels if unit.stride == 2 else 2 * unit.branch2[0].in_channels
+            if cin != real:
+                raise PlanUnsupported("ShuffleNetV2 {}: a unit of {} input channels behind a map of {}".format(uwhat, cin, real))
+            cb = unit.branch2[5].out_channels
+            ok = (N.lib.ssdk_shuffle_down_supported(cin, cb, h, w, plan.dtype_code) if unit.stride == 2
+                  else N.lib.ssdk_shuffle_unit_supported(cb, h, w, plan.dtype_code))
+            if not ok:
+                raise PlanUnsupported("ShuffleNetV2 {}: the kernel's predicate refuses Cin={} Cb={} on {}x{}".format(uwhat, cin, cb, h, w))
+            pk = cls(unit, dt)
+            nxt = plan.shuffle_down(cur, pk) if unit.stride == 2 else plan.shuffle_unit(cur, pk)
+            if not any(cur is o for o in outputs):
+                plan.release(cur)
+            cur = nxt
+        if level in net.outputs:
+            outputs.append(cur)
+    return outputs
+
+
 def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
 def record_backbone(plan, val, net):
-    """Backbone maps of a planned backbone (MobileNet, ResNet, RegNetX, EfficientNet, DarkNet, DenseNet) from the image value;
-    PlanUnsupported otherwise."""
+    """Backbone maps of a planned backbone (MobileNet, ResNet, RegNetX, EfficientNet, DarkNet, DenseNet, ShuffleNetV2) from the image
+    value; PlanUnsupported otherwise."""
+    from ssds.modeling.nets.shufflenet import ShuffleNetV2
     from ssds.modeling.nets.darknet import DarkNet
     from ssds.modeling.nets.densenet import DenseNet
     from ssds.modeling.nets.efficientnet import EfficientEx
@@ -458,6 +547,8 @@ def record_backbone(plan, val, net):
         return record_darknet(plan, val, net)
     if isinstance(net, DenseNet):
         return record_densenet(plan, val, net)
+    if isinstance(net, ShuffleNetV2):
+        return record_shufflenet(plan, val, net)
     raise PlanUnsupported("backbone {} has no planner".format(type(net).__name__))
 
 
@@ -540,10 +631,14 @@ def _neck_inputs(model, features, image):
         plan = ConvPlan(image.device, image.dtype, image.shape)
         return plan, record_backbone(plan, plan.input_value(), model.backbone)
     f0 = features[0]
+    for f in features:
+        if f.shape[1] % 8:  # (a zero-padded map exists only inside a plan that also recorded its backbone)
+            raise PlanUnsupported("a backbone map of {} channels (no multiple of 8) as an external input".format(f.shape[1]))
     plan = ConvPlan(f0.device, f0.dtype)
     return plan, [plan.add_input(f.shape) for f in features]
 
 
+@_one_recording
 def build_fpn_plan(model, features=None, image=None):
     """SSDFPN (ssds/fpn.py) neck + towers -> finalized ConvPlan, on the backbone maps ``features`` (external
     inputs) or, with ``image``, including a planned backbone.  The 1x1 lateral of level i and the nearest-x2
@@ -598,6 +693,7 @@ def _record_bifpn_layer(plan, m, xx):
     return xx
 
 
+@_one_recording
 def build_bifpn_plan(model, features=None, image=None):
     """SSDBiFPN (ssds/bifpn.py): 1x1 transforms, stacked BiFPN layers (weighted fusions as one launch each),
     extras and shared towers -> finalized ConvPlan (inputs as in ``build_fpn_plan``)."""
@@ -659,6 +755,7 @@ def _record_shelf_pyramid(plan, pyr, xx):
     return out[::-1]
 
 
+@_one_recording
 def build_shelf_plan(model, features=None, image=None):
     """SSDShelf (ssds/shelf.py): 1x1 transforms (bias), decoder0 / encoder0 / decoder1 in the reference's orders and
     reversals, the string transforms ("Conv:S") on the last decoder's smallest map, and per level the two ``Head``s
@@ -725,6 +822,7 @@ def _record_heads(plan, model, levels):
             plan.release(mid)
 
 
+@_one_recording
 def build_yolov3_plan(model, features=None, image=None):
     """YOLOV3 (ssds/yolo.py): from the smallest backbone map up, ``extras[i]`` on the concatenation of backbone map i with the
     nearest-x2 upsample of ``transforms[i]`` of the level below (one ssdk_cat2 op: the upsampled tensor is never written); the
@@ -799,6 +897,7 @@ def _record_spp_transform(plan, val, seq):
     return record_chain(plan, pooled, mods[2])
 
 
+@_one_recording
 def build_yolov4_plan(model, features=None, image=None):
     """YOLOV4 (ssds/yolo.py): the 3x3 ``transforms`` (the last one through the SPP block), the stacked PAN modules, the string
     extras behind the last level and per level the two heads -> finalized ConvPlan (inputs as in ``build_fpn_plan``)."""
