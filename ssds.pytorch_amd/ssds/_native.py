@@ -138,29 +138,49 @@ def parse_header(text, struct_names=None):
     return Header(constants, structs, functions)
 
 
-def _read_header():
-    if not os.path.exists(HEADER_PATH):
-        raise ImportError("include/ssdk.h not found at {} -- ssds/_native.py reads the C ABI of libssdk.so from it".format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return parse_header(f.read(), _MIRRORS)
-
-
-# typedef name in the header -> the mirror's name here
+# Every header under include/, ssdk.h first: (file name, {typedef name in the header: the mirror's name here}).  The kernels added
+# after ABI 245 have headers of their own -- the entry points of ssdk.h and the layout of ssdk_op are a closed list under it -- read
+# with the same parser; a new header is one entry here (plus the names it exports below).
 _MIRRORS = collections.OrderedDict((
     ("ssdk_level", "Level"), ("ssdk_conv_desc", "ConvDesc"), ("ssdk_mbconv_desc", "MbConvDesc"), ("ssdk_fuse_desc", "FuseDesc"),
     ("ssdk_stem_desc", "StemDesc"), ("ssdk_pool_desc", "PoolDesc"), ("ssdk_xpair_desc", "XpairDesc"),
     ("ssdk_augment_desc", "AugmentDesc"), ("ssdk_mbse_desc", "MbSeDesc"), ("ssdk_op", "Op")))
+_HEADERS = (
+    ("ssdk.h", _MIRRORS),
+    ("ssdk_convt.h", {"ssdk_convt_desc": "ConvTDesc"}),  # the transposed convolution of the Shelf neck
+    ("ssdk_cat.h", {"ssdk_cat_desc": "CatDesc", "ssdk_spp_desc": "SppDesc"}),  # channel concatenation and SPP block of the YOLO necks
+    ("ssdk_dkres.h", {"ssdk_dkres_desc": "DkresDesc"}),  # the DarkNet residual block as one launch
+    # the DenseNet dense layer as one launch, the front of a transition and the copy into a block's buffer
+    ("ssdk_denselayer.h", {"ssdk_dense_layer_desc": "DenseLayerDesc", "ssdk_dense_pool_desc": "DensePoolDesc",
+                           "ssdk_dense_place_desc": "DensePlaceDesc"}),
+    # the ShuffleNetV2 unit as one launch, stride 1 and stride 2
+    ("ssdk_shuffle.h", {"ssdk_shuffle_unit_desc": "ShuffleUnitDesc", "ssdk_shuffle_down_desc": "ShuffleDownDesc"}),
+    ("ssdk_cattrain.h", {}),  # cat / SPP of the YOLO TRAINING step, forward and backward on NCHW tensors (no descriptors)
+    ("ssdk_convttrain.h", {}),  # the transposed 3x3 / stride 2 of the Shelf TRAINING step, forward and gradients on NCHW tensors
+)
 # the library first: without it nothing below matters, and its message says how to build it -- no header error may mask it
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         "libssdk.so not found at {} -- build it first: `python -c 'import __graft_entry__ as g; "
         "g.build()'` or `make -C ssds.pytorch_amd/csrc` (there is no CPU fallback)".format(LIB_PATH)
     )
-_H = _read_header()
-_K = _H.constants
+_PATHS = [os.path.join(os.path.dirname(HEADER_PATH), _name) for _name, _ in _HEADERS]
+_PARSED = []
+_ABI = Header({}, collections.OrderedDict(), collections.OrderedDict())  # every header's declarations in one place
+for _path, (_name, _mirrors) in zip(_PATHS, _HEADERS):
+    if not os.path.exists(_path):
+        raise ImportError("include/{} not found at {} -- ssds/_native.py reads the C ABI of libssdk.so from it".format(_name, _path))
+    with open(_path) as _f:
+        _PARSED.append(parse_header(_f.read(), _mirrors))
+    for _merged, _part in zip(_ABI, _PARSED[-1]):
+        _merged.update(_part)
+_K = _ABI.constants
 
 ABI_VERSION = _K["SSDK_VERSION"]  # a library of an older version is refused by _load
-EXPORTS = tuple(_H.functions)
+(EXPORTS, CONVT_EXPORTS, CAT_EXPORTS, DKRES_EXPORTS, DENSE_EXPORTS, SHUFFLE_EXPORTS, CATTRAIN_EXPORTS,
+ CONVTTRAIN_EXPORTS) = (tuple(_h.functions) for _h in _PARSED)
+(_, CONVT_HEADER_PATH, CAT_HEADER_PATH, DKRES_HEADER_PATH, DENSE_HEADER_PATH, SHUFFLE_HEADER_PATH, CATTRAIN_HEADER_PATH,
+ CONVTTRAIN_HEADER_PATH) = _PATHS
 
 MAX_LEVELS, MAX_ANCHORS, MAX_TOPN, MAX_NDET, MAX_NMS_N, MAX_GT = (
     _K["SSDK_MAX_" + n] for n in ("LEVELS", "ANCHORS", "TOPN", "NDET", "NMS_N", "GT"))
@@ -177,98 +197,31 @@ FUSE_SAME, FUSE_UP2, FUSE_POOL2 = _K["SSDK_FUSE_SAME"], _K["SSDK_FUSE_UP2"], _K[
 NCHW, NHWC = _K["SSDK_LAYOUT_NCHW"], _K["SSDK_LAYOUT_NHWC"]
 
 Level, ConvDesc, MbConvDesc, FuseDesc, StemDesc, PoolDesc, XpairDesc, AugmentDesc, MbSeDesc, Op = (
-    _H.structs[cname] for cname in _MIRRORS)
+    _ABI.structs[cname] for cname in _MIRRORS)
+ConvTDesc, CatDesc, SppDesc, DkresDesc = (_ABI.structs["ssdk_%s_desc" % n] for n in ("convt", "cat", "spp", "dkres"))
+DenseLayerDesc, DensePoolDesc, DensePlaceDesc = (_ABI.structs["ssdk_dense_%s_desc" % n] for n in ("layer", "pool", "place"))
+ShuffleUnitDesc, ShuffleDownDesc = _ABI.structs["ssdk_shuffle_unit_desc"], _ABI.structs["ssdk_shuffle_down_desc"]
 AugmentDesc.__doc__ = ("ssdk_augment_desc: one image of an ssdk_augment batch (ssds/dataset/augment.py DESC_DTYPE is the numpy "
                        "view of it).")
 MbSeDesc.__doc__ = "ssdk_mbse_desc: the tail of an EfficientNet MBConv block (depthwise + SE gate + gated projection)."
-
-# include/ssdk_convt.h: the transposed convolution of the Shelf neck.  A header of its own -- the entry points of ssdk.h and the
-# layout of ssdk_op are a closed list under ABI 245 -- read with the same parser; its entry points are bound next to EXPORTS.
-CONVT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_convt.h")
-if not os.path.exists(CONVT_HEADER_PATH):
-    raise ImportError("include/ssdk_convt.h not found at {} -- ssds/_native.py reads the transposed convolution's C ABI from it".format(
-        CONVT_HEADER_PATH))
-with open(CONVT_HEADER_PATH) as _f:
-    _HT = parse_header(_f.read(), {"ssdk_convt_desc": "ConvTDesc"})
-CONVT_EXPORTS = tuple(_HT.functions)
-ConvTDesc = _HT.structs["ssdk_convt_desc"]
 ConvTDesc.__doc__ = "ssdk_convt_desc: transposed 3x3 / stride 2 / pad 1 convolution + bias (+ skip), the Shelf decoder step."
-
-# include/ssdk_cat.h: the channel concatenation and the SPP block of the YOLO necks, a header of its own for the same reason
-CAT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_cat.h")
-if not os.path.exists(CAT_HEADER_PATH):
-    raise ImportError("include/ssdk_cat.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_cat2 / ssdk_spp from it".format(
-        CAT_HEADER_PATH))
-with open(CAT_HEADER_PATH) as _f:
-    _HC = parse_header(_f.read(), {"ssdk_cat_desc": "CatDesc", "ssdk_spp_desc": "SppDesc"})
-CAT_EXPORTS = tuple(_HC.functions)
-CatDesc, SppDesc = _HC.structs["ssdk_cat_desc"], _HC.structs["ssdk_spp_desc"]
 CatDesc.__doc__ = "ssdk_cat_desc: y = a || b, or a || nearest_x2(b), along the channels (YOLOv3 / PAN concatenations)."
 SppDesc.__doc__ = "ssdk_spp_desc: y = x || maxpool5(x) || maxpool9(x) || maxpool13(x) (the SPP block of YOLOv4)."
-
-# include/ssdk_dkres.h: the DarkNet residual block as one launch, a header of its own for the same reason
-DKRES_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_dkres.h")
-if not os.path.exists(DKRES_HEADER_PATH):
-    raise ImportError("include/ssdk_dkres.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_dkres from it".format(
-        DKRES_HEADER_PATH))
-with open(DKRES_HEADER_PATH) as _f:
-    _HD = parse_header(_f.read(), {"ssdk_dkres_desc": "DkresDesc"})
-DKRES_EXPORTS = tuple(_HD.functions)
-DkresDesc = _HD.structs["ssdk_dkres_desc"]
 DkresDesc.__doc__ = "ssdk_dkres_desc: y = x + act2(bn2(conv3x3(act1(bn1(conv1x1(x)))))), the DarkNet residual block in one launch."
-DKRES_TILE_H, DKRES_TILE_W = _HD.constants["SSDK_DKRES_TILE_H"], _HD.constants["SSDK_DKRES_TILE_W"]  # a workgroup's output tile
-
-# include/ssdk_denselayer.h: the DenseNet dense layer as one launch, the front of a transition and the copy into a block's buffer
-DENSE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_denselayer.h")
-if not os.path.exists(DENSE_HEADER_PATH):
-    raise ImportError("include/ssdk_denselayer.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_dense_layer from it".format(
-        DENSE_HEADER_PATH))
-with open(DENSE_HEADER_PATH) as _f:
-    _HDN = parse_header(_f.read(), {"ssdk_dense_layer_desc": "DenseLayerDesc", "ssdk_dense_pool_desc": "DensePoolDesc",
-                                    "ssdk_dense_place_desc": "DensePlaceDesc"})
-DENSE_EXPORTS = tuple(_HDN.functions)
-DenseLayerDesc, DensePoolDesc, DensePlaceDesc = (_HDN.structs["ssdk_dense_%s_desc" % n] for n in ("layer", "pool", "place"))
 DenseLayerDesc.__doc__ = ("ssdk_dense_layer_desc: y[Cin : Cin + 32] = conv3x3(relu(bn2(conv1x1(relu(bn1(x[:Cin])))))) in one launch, x and y "
                           "in one buffer of pixel stride ld.")
 DensePoolDesc.__doc__ = "ssdk_dense_pool_desc: y = avgpool2x2(relu(a * x + b)), x with pixel stride ld (the front of a DenseNet transition)."
 DensePlaceDesc.__doc__ = "ssdk_dense_place_desc: a dense NHWC tensor copied into channels [0, C) of a buffer with pixel stride ld."
-DENSE_TILE_H, DENSE_TILE_W = _HDN.constants["SSDK_DENSE_TILE_H"], _HDN.constants["SSDK_DENSE_TILE_W"]  # a workgroup's output tile
-DENSE_CMID, DENSE_COUT = _HDN.constants["SSDK_DENSE_CMID"], _HDN.constants["SSDK_DENSE_COUT"]
-
-# include/ssdk_shuffle.h: the ShuffleNetV2 unit as one launch, stride 1 and stride 2
-SHUFFLE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_shuffle.h")
-if not os.path.exists(SHUFFLE_HEADER_PATH):
-    raise ImportError("include/ssdk_shuffle.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_shuffle_unit from it".format(
-        SHUFFLE_HEADER_PATH))
-with open(SHUFFLE_HEADER_PATH) as _f:
-    _HSF = parse_header(_f.read(), {"ssdk_shuffle_unit_desc": "ShuffleUnitDesc", "ssdk_shuffle_down_desc": "ShuffleDownDesc"})
-SHUFFLE_EXPORTS = tuple(_HSF.functions)
-ShuffleUnitDesc, ShuffleDownDesc = _HSF.structs["ssdk_shuffle_unit_desc"], _HSF.structs["ssdk_shuffle_down_desc"]
 ShuffleUnitDesc.__doc__ = ("ssdk_shuffle_unit_desc: y[2i] = x[i], y[2i + 1] = branch2(x[Cb:])[i] -- the stride-1 ShuffleNetV2 unit in one "
                            "launch, the channel shuffle in the store.")
 ShuffleDownDesc.__doc__ = "ssdk_shuffle_down_desc: y[2i] = branch1(x)[i], y[2i + 1] = branch2(x)[i] -- the stride-2 unit in one launch."
-SHUFFLE_TILE_H, SHUFFLE_TILE_W = _HSF.constants["SSDK_SHUFFLE_TILE_H"], _HSF.constants["SSDK_SHUFFLE_TILE_W"]  # a workgroup's output tile
-SHUFFLE_DOWN_TILE_H, SHUFFLE_DOWN_TILE_W = _HSF.constants["SSDK_SHUFFLE_DOWN_TILE_H"], _HSF.constants["SSDK_SHUFFLE_DOWN_TILE_W"]
-SHUFFLE_CHUNK = _HSF.constants["SSDK_SHUFFLE_CHUNK"]  # weight images and vectors are zero-padded to a multiple of it
-
-# include/ssdk_cattrain.h: the same two operations of the YOLO TRAINING step, forward and backward on NCHW tensors (no descriptors)
-CATTRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_cattrain.h")
-if not os.path.exists(CATTRAIN_HEADER_PATH):
-    raise ImportError("include/ssdk_cattrain.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_cat_train_* / "
-                      "ssdk_spp_train_* from it".format(CATTRAIN_HEADER_PATH))
-with open(CATTRAIN_HEADER_PATH) as _f:
-    _HCT = parse_header(_f.read())
-CATTRAIN_EXPORTS = tuple(_HCT.functions)
-SPP_TRAIN_MAX_SIDE = _HCT.constants["SSDK_SPP_TRAIN_MAX_SIDE"]  # the largest H / W ssdk_spp_train_* stage in LDS
-
-# include/ssdk_convttrain.h: the transposed 3x3 / stride 2 of the Shelf TRAINING step, forward and gradients on NCHW tensors
-CONVTTRAIN_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ssdk_convttrain.h")
-if not os.path.exists(CONVTTRAIN_HEADER_PATH):
-    raise ImportError("include/ssdk_convttrain.h not found at {} -- ssds/_native.py reads the C ABI of ssdk_convt_train_* from "
-                      "it".format(CONVTTRAIN_HEADER_PATH))
-with open(CONVTTRAIN_HEADER_PATH) as _f:
-    _HTT = parse_header(_f.read())
-CONVTTRAIN_EXPORTS = tuple(_HTT.functions)
+DKRES_TILE_H, DKRES_TILE_W = _K["SSDK_DKRES_TILE_H"], _K["SSDK_DKRES_TILE_W"]  # a workgroup's output tile
+DENSE_TILE_H, DENSE_TILE_W = _K["SSDK_DENSE_TILE_H"], _K["SSDK_DENSE_TILE_W"]
+DENSE_CMID, DENSE_COUT = _K["SSDK_DENSE_CMID"], _K["SSDK_DENSE_COUT"]
+SHUFFLE_TILE_H, SHUFFLE_TILE_W = _K["SSDK_SHUFFLE_TILE_H"], _K["SSDK_SHUFFLE_TILE_W"]
+SHUFFLE_DOWN_TILE_H, SHUFFLE_DOWN_TILE_W = _K["SSDK_SHUFFLE_DOWN_TILE_H"], _K["SSDK_SHUFFLE_DOWN_TILE_W"]
+SHUFFLE_CHUNK = _K["SSDK_SHUFFLE_CHUNK"]  # weight images and vectors are zero-padded to a multiple of it
+SPP_TRAIN_MAX_SIDE = _K["SSDK_SPP_TRAIN_MAX_SIDE"]  # the largest H / W ssdk_spp_train_* stage in LDS
 
 
 def _load():
@@ -276,8 +229,7 @@ def _load():
 
     def bind(name):
         fn = getattr(lib, name)
-        fn.restype, fn.argtypes = (_H.functions.get(name) or _HT.functions.get(name) or _HC.functions.get(name)
-                                   or _HD.functions.get(name) or _HDN.functions.get(name) or _HSF.functions.get(name) or _HCT.functions.get(name) or _HTT.functions[name])
+        fn.restype, fn.argtypes = _ABI.functions[name]
         return fn
 
     # version FIRST: a library older than ABI 230 has no ssdk_struct_size, and a bare AttributeError from the symbol lookup
@@ -289,41 +241,30 @@ def _load():
     if have < ABI_VERSION:
         raise ImportError("libssdk.so at {} is ABI {} but ssds/_native.py is written for ABI {}: rebuild it "
                           "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, have, ABI_VERSION))
-    for name in EXPORTS + CONVT_EXPORTS + CAT_EXPORTS + DKRES_EXPORTS + DENSE_EXPORTS + SHUFFLE_EXPORTS + CATTRAIN_EXPORTS + CONVTTRAIN_EXPORTS:
+    for name in _ABI.functions:
         try:
             bind(name)
         except AttributeError:
-            raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h (or ssdk_convt.h, ssdk_cat.h, ssdk_dkres.h, "
-                              "ssdk_denselayer.h, ssdk_shuffle.h, ssdk_cattrain.h, ssdk_convttrain.h next to it) declares: rebuild it "
-                              "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, name))
+            raise ImportError("libssdk.so at {} does not export {}, which include/ssdk.h (or {} next to it) declares: rebuild it "
+                              "(`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, name, ", ".join(n for n, _ in _HEADERS[1:])))
     # the ctypes mirrors must have the layout the library was BUILT with: a shorter struct would be read past its end.
     # SSDK_SIZEOF_X is the index of struct ssdk_x
     for key, which in sorted((kv for kv in _K.items() if kv[0].startswith("SSDK_SIZEOF_")), key=lambda kv: kv[1]):
-        cls = _H.structs["ssdk_" + key[len("SSDK_SIZEOF_"):].lower()]
+        cls = _ABI.structs["ssdk_" + key[len("SSDK_SIZEOF_"):].lower()]
         want = lib.ssdk_struct_size(which)
         if want != ctypes.sizeof(cls):
             raise ImportError("libssdk.so at {} was built against another include/ssdk.h: sizeof({}) is {} there, {} in ssds/_native.py"
                               .format(LIB_PATH, cls.__name__, want, ctypes.sizeof(cls)))
     if lib.ssdk_abi_check(ABI_VERSION, ctypes.sizeof(Op)) != 0:
         raise ImportError("libssdk.so at {}: {}".format(LIB_PATH, lib.ssdk_last_error().decode()))
-    # ssdk_augment_desc, ssdk_mbse_desc, ssdk_convt_desc (ssdk_convt.h), ssdk_cat_desc and ssdk_spp_desc (ssdk_cat.h) are not behind
-    # ssdk_struct_size (its eight indices are part of ABI 245): the library reports their sizes itself
-    mirrors = dict(_H.structs, **_HT.structs)
-    mirrors.update(_HC.structs)
-    mirrors.update(_HD.structs)
-    mirrors.update(_HDN.structs)
-    mirrors.update(_HSF.structs)
-    for cname, fn in (("ssdk_augment_desc", lib.ssdk_augment_desc_bytes), ("ssdk_mbse_desc", lib.ssdk_mbse_desc_bytes),
-                      ("ssdk_convt_desc", lib.ssdk_convt_desc_bytes), ("ssdk_cat_desc", lib.ssdk_cat_desc_bytes),
-                      ("ssdk_spp_desc", lib.ssdk_spp_desc_bytes), ("ssdk_dkres_desc", lib.ssdk_dkres_desc_bytes),
-                      ("ssdk_dense_layer_desc", lib.ssdk_dense_layer_desc_bytes), ("ssdk_dense_pool_desc", lib.ssdk_dense_pool_desc_bytes),
-                      ("ssdk_dense_place_desc", lib.ssdk_dense_place_desc_bytes),
-                      ("ssdk_shuffle_unit_desc", lib.ssdk_shuffle_unit_desc_bytes),
-                      ("ssdk_shuffle_down_desc", lib.ssdk_shuffle_down_desc_bytes)):
-        if int(fn()) != ctypes.sizeof(mirrors[cname]):
-            raise ImportError("libssdk.so at {} has sizeof({}) = {} but ssds/_native.py mirrors it with {} bytes: "
-                              "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, cname, int(fn()),
-                                                                                   ctypes.sizeof(mirrors[cname])))
+    # the structs that are not behind ssdk_struct_size (its eight indices are part of ABI 245) have an entry point that reports
+    # their size: ssdk_x_desc -> ssdk_x_desc_bytes
+    for cname, cls in _ABI.structs.items():
+        if cname + "_bytes" in _ABI.functions:
+            want = int(getattr(lib, cname + "_bytes")())
+            if want != ctypes.sizeof(cls):
+                raise ImportError("libssdk.so at {} has sizeof({}) = {} but ssds/_native.py mirrors it with {} bytes: "
+                                  "rebuild it (`make -C ssds.pytorch_amd/csrc`)".format(LIB_PATH, cname, want, ctypes.sizeof(cls)))
     return lib
 
 

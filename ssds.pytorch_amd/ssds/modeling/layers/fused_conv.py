@@ -13,6 +13,7 @@
 Switch: ``SSDK_FUSED_CONV`` = "1" (default: HIP kernels in eval mode on a HIP device) or "0" (torch/MIOpen
 everywhere; for A/B measurements only, never chosen silently).
 """
+import collections
 import ctypes
 import contextlib
 import os
@@ -347,6 +348,18 @@ def _out_tensor(y, shape, like, memory_format, what):
     return y
 
 
+def _out_shape(kind, **L):
+    """(c, ho, wo) of an op of ``kind`` on the layer-dict entries ``L``: the op table's geometry (``OP_KINDS[kind].out``), for the
+    ``*_native`` wrappers, which have no layer dict."""
+    return OP_KINDS[kind].out(L)
+
+
+def fill_stem_desc(d, x_ptr, y_ptr, n, h, w, cin, pack, dtype_code, in_layout):
+    d.x, d.w, d.scale, d.bias, d.y = x_ptr, pack.w.data_ptr(), pack.scale.data_ptr(), pack.bias.data_ptr(), y_ptr
+    d.N, d.H, d.W, d.Cin, d.Cout, d.act, d.dtype, d.in_layout = n, h, w, cin, pack.cout, N.ACT[pack.act], dtype_code, in_layout
+    return d
+
+
 def stem7_native(x, pack, y=None):
     """[N,3,H,W] image (NCHW contiguous or channels_last) -> channels_last [N,Cout,H/2,W/2] (``y``: write there)."""
     N.require_device(x, "conv_stem7")
@@ -355,15 +368,18 @@ def stem7_native(x, pack, y=None):
     if not x.is_contiguous():
         x = x.contiguous(memory_format=torch.channels_last)
         layout = N.NHWC
-    ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
-    y = _out_tensor(y, (n, pack.cout, ho, wo), x, torch.channels_last, "conv_stem7")
-    d = N.StemDesc()
-    d.x, d.w, d.scale, d.bias, d.y = x.data_ptr(), pack.w.data_ptr(), pack.scale.data_ptr(), pack.bias.data_ptr(), y.data_ptr()
-    d.N, d.H, d.W, d.Cin, d.Cout, d.act, d.dtype, d.in_layout = n, h, w, c, pack.cout, N.ACT[pack.act], N.dtype_code(x), layout
+    y = _out_tensor(y, (n,) + _out_shape("stem7", pack=pack, h=h, w=w), x, torch.channels_last, "conv_stem7")
+    d = fill_stem_desc(N.StemDesc(), x.data_ptr(), y.data_ptr(), n, h, w, c, pack, N.dtype_code(x), layout)
     with torch.cuda.device(x.device):
         rc = N.lib.ssdk_conv_stem7(ctypes.byref(d), N.stream_ptr(x.device))
     N.check(rc, "conv_stem7")
     return y
+
+
+def fill_pool_desc(d, x_ptr, y_ptr, n, h, w, c, dtype_code):
+    d.x, d.y = x_ptr, y_ptr
+    d.N, d.H, d.W, d.C, d.dtype = n, h, w, c, dtype_code
+    return d
 
 
 def maxpool_native(x, y=None):
@@ -372,11 +388,8 @@ def maxpool_native(x, y=None):
     if not x.is_contiguous(memory_format=torch.channels_last):
         x = x.contiguous(memory_format=torch.channels_last)
     n, c, h, w = (int(v) for v in x.shape)
-    ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-    y = _out_tensor(y, (n, c, ho, wo), x, torch.channels_last, "maxpool3x3s2")
-    d = N.PoolDesc()
-    d.x, d.y = x.data_ptr(), y.data_ptr()
-    d.N, d.H, d.W, d.C, d.dtype = n, h, w, c, N.dtype_code(x)
+    y = _out_tensor(y, (n,) + _out_shape("pool", ch=c, h=h, w=w), x, torch.channels_last, "maxpool3x3s2")
+    d = fill_pool_desc(N.PoolDesc(), x.data_ptr(), y.data_ptr(), n, h, w, c, N.dtype_code(x))
     with torch.cuda.device(x.device):
         rc = N.lib.ssdk_maxpool3x3s2(ctypes.byref(d), N.stream_ptr(x.device))
     N.check(rc, "maxpool3x3s2")
@@ -675,7 +688,7 @@ def mbse_native(x, pk, residual=None, stages=0, t=None, pool_partial=None, gate=
     if not x.is_contiguous(memory_format=torch.channels_last):
         x = x.contiguous(memory_format=torch.channels_last)
     n, c, h, w = (int(v) for v in x.shape)
-    ho, wo = _out_hw(h, w, pk.k, pk.stride)
+    _, ho, wo = _out_shape("mbse", pack=pk, h=h, w=w)
     tiles = mbse_pool_tiles(h, w, pk.k, pk.stride)
     dev = x.device
     t = torch.empty((n, c, ho, wo), device=dev, dtype=x.dtype, memory_format=torch.channels_last) if t is None else t
@@ -758,7 +771,7 @@ def convt_native(x, pk, skip=None, act="none", y=None):
     n, c, h, w = (int(v) for v in x.shape)
     assert c == pk.cin, (c, pk.cin)
     if y is None:
-        y = torch.empty((n, pk.cout, 2 * h - 1, 2 * w - 1), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+        y = torch.empty((n,) + _out_shape("convt", pack=pk, h=h, w=w), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
     if skip is not None:
         assert tuple(skip.shape) == tuple(y.shape) and skip.dtype == x.dtype, (tuple(skip.shape), tuple(y.shape))
         if not skip.is_contiguous(memory_format=torch.channels_last):
@@ -872,8 +885,7 @@ def xpair_native(x, p1, p2, y=None):
     if not x.is_contiguous(memory_format=torch.channels_last):
         x = x.contiguous(memory_format=torch.channels_last)
     n, c, h, w = (int(v) for v in x.shape)
-    ho, wo = _out_hw(h, w, 3, 2)
-    y = _out_tensor(y, (n, p2.cout, ho, wo), x, torch.channels_last, "xpair")
+    y = _out_tensor(y, (n,) + _out_shape("xpair", pack2=p2, h=h, w=w), x, torch.channels_last, "xpair")
     d = fill_xpair_desc(N.XpairDesc(), x.data_ptr(), y.data_ptr(), n, h, w, p1, p2, N.dtype_code(x))
     with torch.cuda.device(x.device):
         rc = N.lib.ssdk_xpair(ctypes.byref(d), N.stream_ptr(x.device))
@@ -1043,7 +1055,7 @@ def dense_layer_native(buf, pk):
 def dense_pool_native(buf, c, a, b, y=None):
     """avgpool2x2(relu(a * buf[..., :c] + b)) -> channels_last [N, c, H/2, W/2] (``y``: write there)."""
     n, h, w, ld = _dense_buffer(buf, "dense_pool")
-    y = _out_tensor(y, (n, c, h // 2, w // 2), buf, torch.channels_last, "dense_pool")
+    y = _out_tensor(y, (n,) + _out_shape("densepool", ch=c, h=h, w=w), buf, torch.channels_last, "dense_pool")
     d = N.DensePoolDesc()
     d.x, d.y, d.a, d.b = buf.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr()
     d.N, d.H, d.W, d.C, d.ld, d.dtype = n, h, w, c, ld, N.dtype_code(buf)
@@ -1292,13 +1304,27 @@ def shuffle_down_native(x, pk, y=None):
     n, h, w, ld = _nhwc(x, "shuffle_down")
     if ld < pk.cin or ld % 8:
         raise N.SsdkError("shuffle_down: x has {} channels per pixel, a unit of Cin = {} needs a multiple of 8 >= Cin".format(ld, pk.cin))
-    y = _out_tensor(y, (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, pad8(2 * pk.cb)), x, torch.contiguous_format, "shuffle_down")
+    cp, ho, wo = _out_shape("shuffledown", pack=pk, h=h, w=w)
+    y = _out_tensor(y, (n, ho, wo, cp), x, torch.contiguous_format, "shuffle_down")
     d = fill_shuffle_desc(N.ShuffleDownDesc(), x.data_ptr(), y.data_ptr(), n, h, w, pk, N.dtype_code(x), ld_in=ld)
     with torch.cuda.device(x.device):
         rc = N.lib.ssdk_shuffle_down(ctypes.byref(d), N.stream_ptr(x.device))
     N.check(rc, "shuffle_down")
     STATS["native_layers"] += 5
     return y
+
+
+def fill_fuse_desc(d, a_ptr, b_ptr, c_ptr, y_ptr, n, h, w, ch, weights, mode_b, mode_c, hw_b, hw_c, dtype_code):
+    """``hw_b`` / ``hw_c``: (height, width) of the sources b and c (``hw_c`` None without a third source)."""
+    d.a, d.b, d.c, d.y = a_ptr, b_ptr, c_ptr, y_ptr
+    d.w0, d.w1, d.w2 = (float(v) for v in weights)
+    d.mode_b, d.mode_c = mode_b, mode_c
+    d.N, d.H, d.W, d.C = n, h, w, ch
+    d.hb, d.wb = (int(v) for v in hw_b)
+    if hw_c is not None:
+        d.hc, d.wc = (int(v) for v in hw_c)
+    d.dtype = dtype_code
+    return d
 
 
 def fuse_native(a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_c=N.FUSE_SAME, y=None):
@@ -1310,15 +1336,8 @@ def fuse_native(a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_
     a, b, c = ts
     n, ch, h, w = (int(v) for v in a.shape)
     y = _out_tensor(y, (n, ch, h, w), a, torch.channels_last, "fuse")
-    d = N.FuseDesc()
-    d.a, d.b, d.c, d.y = a.data_ptr(), b.data_ptr(), (c.data_ptr() if c is not None else None), y.data_ptr()
-    d.w0, d.w1, d.w2 = (float(v) for v in weights)
-    d.mode_b, d.mode_c = mode_b, mode_c
-    d.N, d.H, d.W, d.C = n, h, w, ch
-    d.hb, d.wb = int(b.shape[2]), int(b.shape[3])
-    if c is not None:
-        d.hc, d.wc = int(c.shape[2]), int(c.shape[3])
-    d.dtype = N.dtype_code(a)
+    d = fill_fuse_desc(N.FuseDesc(), a.data_ptr(), b.data_ptr(), c.data_ptr() if c is not None else None, y.data_ptr(), n, h, w, ch,
+                       weights, mode_b, mode_c, tuple(b.shape[2:]), tuple(c.shape[2:]) if c is not None else None, N.dtype_code(a))
     with torch.cuda.device(a.device):
         rc = N.lib.ssdk_fuse(ctypes.byref(d), N.stream_ptr(a.device))
     N.check(rc, "fuse")
@@ -1337,9 +1356,7 @@ def mbconv_native(x, pk, variant=0, y=None):
             x = x.contiguous(memory_format=torch.channels_last)
         stem = 2 if stem else 0
     n, c, h, w = (int(v) for v in x.shape)
-    hs, ws = _out_hw(h, w, 3, 2) if pk.stem else (h, w)
-    ho, wo = _out_hw(hs, ws, 3, pk.stride)
-    y = _out_tensor(y, (n, pk.cout, ho, wo), x, torch.channels_last, "mbconv")
+    y = _out_tensor(y, (n,) + _out_shape("mb", pack=pk, h=h, w=w), x, torch.channels_last, "mbconv")
     d = fill_mb_desc(N.MbConvDesc(), x.data_ptr(), y.data_ptr(), n, h, w, pk, N.dtype_code(x))
     d.stem = stem
     d.variant = int(variant)
@@ -1404,7 +1421,7 @@ def conv_native(x, pack, act=None, residual=None, nchw_out=False, split=None, ac
         in_layout = N.NCHW
     elif not x.is_contiguous(memory_format=torch.channels_last):
         x = x.contiguous(memory_format=torch.channels_last)
-    ho, wo = _out_hw(h, w, pack.k, pack.stride)
+    _, ho, wo = _out_shape(None, pack=pack, h=h, w=w)
     if y2 is not None and not (nchw_out and split is not None):
         raise N.SsdkError("conv: y2 is the second output of a split NCHW head; this call has none")
     if nchw_out:
@@ -1432,6 +1449,300 @@ def conv_native(x, pack, act=None, residual=None, nchw_out=False, split=None, ac
     N.check(rc, "conv")
     STATS["native_layers"] += 1
     return (y, y2) if y2 is not None else y
+
+
+# ---- the plan's op kinds: ONE definition each of the executor's op code, the output geometry, the descriptor fill and the table row.
+# ``out(L)`` -> (c, ho, wo), the output's shape from the layer dict alone (what the record methods allocate and the ``*_native``
+# wrappers return); ``fill(plan, i, L, op)`` fills ``plan.ops[i]`` (a source that is an external input goes through ``plan._ptr``,
+# which notes the patch); ``row(L, es)`` -> dict(name, flops = 2 * MAC, bytes = algorithmic HBM traffic, kind) of ``layer_table()``.
+# A new plan op = a record method of ConvPlan + one entry of OP_KINDS + one dispatch line in ssdk_run_ops (csrc/ssdk_conv.hip).
+OpKind = collections.namedtuple("OpKind", "code out fill row")
+
+
+def _pnhw(L):
+    return L["pack"], L["n"], L["h"], L["w"]
+
+
+def _conv_out(L):
+    pk = L["pack"]
+    return (pk.cout,) + _out_hw(L["h"], L["w"], pk.k, pk.stride)
+
+
+def _conv_fill(plan, i, L, op):
+    y_ptr = plan.arena.ptr(L["y"]) if L["y"] is not None else 0
+    res_ptr = plan._ptr(L["res"], plan.patches, i, "conv.residual") if L["res"] is not None else None
+    fill_desc(op.conv, plan._ptr(L["x"], plan.patches, i, "conv.x"), L["n"], L["h"], L["w"], L["pack"],
+              plan.dtype_code, L["act"], y_ptr, N.NHWC, N.NCHW if L["nchw"] else N.NHWC, res_ptr, None,
+              L.get("split"), L.get("act2"))
+    op.conv.res_mode = L.get("res_mode", 0)
+
+
+def _conv_row(L, es):
+    pk, n, h, w = _pnhw(L)
+    _, ho, wo = _conv_out(L)
+    macs = n * ho * wo * pk.cout * (pk.cin // pk.groups) * pk.k * pk.k
+    byt = es * (n * (h * w * pk.cin + ho * wo * pk.cout) + pk.cout * (pk.cin // pk.groups) * pk.k * pk.k)
+    kind = "head" if L["nchw"] else ("tower" if L.get("role") == "tower" else
+                                     ("dw" if pk.kind == "dw" else ("gconv" if pk.groups > 1 else "conv")))
+    return dict(name="%s %d>%d k%d s%d @%dx%d" % (kind, pk.cin, pk.cout, pk.k, pk.stride, h, w),
+                flops=2.0 * macs, bytes=float(byt), kind=kind)
+
+
+def _mb_out(L):
+    pk = L["pack"]
+    hs, ws = _out_hw(L["h"], L["w"], 3, 2) if pk.stem else (L["h"], L["w"])
+    return (pk.cout,) + _out_hw(hs, ws, 3, pk.stride)
+
+
+def _mb_fill(plan, i, L, op):
+    fill_mb_desc(op.mb, plan._ptr(L["x"], plan.patches, i, "mb.x"), plan.arena.ptr(L["y"]), L["n"], L["h"],
+                 L["w"], L["pack"], plan.dtype_code)
+
+
+def _mb_row(L, es):
+    pk, n, h, w = _pnhw(L)
+    _, ho, wo = _mb_out(L)
+    if pk.stem:  # stem 3x3/s2 (cin -> chid) + depthwise + projection
+        hs, ws = _out_hw(h, w, 3, 2)
+        macs = n * (hs * ws * 9 * pk.cin * pk.chid + ho * wo * 9 * pk.chid + ho * wo * pk.chid * pk.cout)
+    else:
+        macs = n * (h * w * pk.cin * pk.chid + ho * wo * 9 * pk.chid + ho * wo * pk.chid * pk.cout)
+    byt = es * n * (h * w * pk.cin + ho * wo * pk.cout)
+    name = "mbconv%s %d>%d>%d s%d @%dx%d" % ("+stem" if pk.stem else "", pk.cin, pk.chid, pk.cout, pk.stride, h, w)
+    return dict(name=name, flops=2.0 * macs, bytes=float(byt), kind="mbconv")
+
+
+def _mbse_fill(plan, i, L, op):
+    fill_mbse_desc(op.mbse, L["pack"], L["n"], L["h"], L["w"], plan.dtype_code,
+                   plan._ptr(L["x"], plan.patches, i, "mbse.x"), plan.arena.ptr(L["t"]), plan.arena.ptr(L["partial"]),
+                   plan.arena.ptr(L["gate"]), plan.arena.ptr(L["y"]),
+                   plan._ptr(L["res"], plan.patches, i, "mbse.residual") if L["res"] is not None else None)
+
+
+def _mbse_row(L, es):  # depthwise + SE + gated projection: x in, y out, t written and read once, the weights
+    pk, n, h, w = _pnhw(L)
+    _, ho, wo = _conv_out(L)
+    macs = n * (ho * wo * pk.k * pk.k * pk.cin + 2 * pk.cin * pk.r + ho * wo * pk.cin * pk.cout)
+    byt = (es * (n * (h * w * pk.cin + 2 * ho * wo * pk.cin + ho * wo * pk.cout) + pk.k * pk.k * pk.cin
+                 + pk.cin * pk.cout) + 4 * (2 * pk.cin * pk.r + pk.r + pk.cin))
+    return dict(name="mbse %d>%d k%d s%d @%dx%d" % (pk.cin, pk.cout, pk.k, pk.stride, h, w), flops=2.0 * macs,
+                bytes=float(byt), kind="mbconv")
+
+
+def _convt_out(L):
+    return (L["pack"].cout, 2 * L["h"] - 1, 2 * L["w"] - 1)
+
+
+def _carried(plan, i, L, op, cin, cout, k, stride, split, act="none"):
+    """What the kinds carried by the op's ssdk_conv_desc under other field names (include/ssdk.h SSDK_OP_CONVT, _CAT, _SPP,
+    _DENSEPOOL, _DENSEPLACE) fill alike; -> the descriptor for the kind's own fields."""
+    c = op.conv
+    c.x, c.y = plan._ptr(L["x"], plan.patches, i, "conv.x"), plan.arena.ptr(L["y"])
+    c.N, c.Cin, c.H, c.W, c.Cout, c.k, c.stride, c.groups = L["n"], cin, L["h"], L["w"], cout, k, stride, 1
+    c.act, c.act2 = N.ACT[act], N.ACT["none"]
+    c.split, c.dtype, c.in_layout, c.out_layout = split, plan.dtype_code, N.NHWC, N.NHWC
+    return c
+
+
+def _convt_fill(plan, i, L, op):  # w = the parity images
+    pk = L["pack"]
+    c = _carried(plan, i, L, op, pk.cin, pk.cout, 3, 2, pk.cout)
+    c.w = pk.w.data_ptr()
+    c.bias = pk.bias.data_ptr() if pk.bias is not None else None
+    c.residual = plan._ptr(L["res"], plan.patches, i, "conv.residual") if L["res"] is not None else None
+
+
+def _convt_row(L, es):  # 9 taps per 2 x 2 output quad, less the last row / column's; x, skip, y and the weights once
+    pk, n, h, w = _pnhw(L)
+    _, ho, wo = _convt_out(L)
+    macs = n * pk.cin * pk.cout * (h * w + 2 * h * (w - 1) + 2 * (h - 1) * w + 4 * (h - 1) * (w - 1))
+    byt = es * (n * (h * w * pk.cin + (2 if L["res"] is not None else 1) * ho * wo * pk.cout) + 9 * pk.cin * pk.cout)
+    return dict(name="convt %d>%d k3 s2 @%dx%d" % (pk.cin, pk.cout, h, w), flops=2.0 * macs, bytes=float(byt), kind="conv")
+
+
+def _cat_fill(plan, i, L, op):
+    c = _carried(plan, i, L, op, L["c1"], L["c1"] + L["c2"], 1, 1, L["c1"] + L["c2"])
+    c.residual, c.res_mode = plan._ptr(L["b"], plan.patches, i, "conv.residual"), 1 if L["up2"] else 0
+
+
+def _cat_row(L, es):  # data movement: both sources and the output once
+    n, h, w, c1, c2 = L["n"], L["h"], L["w"], L["c1"], L["c2"]
+    src_b = (h // 2) * (w // 2) if L["up2"] else h * w
+    return dict(name="cat %d+%d%s @%dx%d" % (c1, c2, " up2" if L["up2"] else "", h, w), flops=0.0,
+                bytes=float(es * n * (h * w * c1 + src_b * c2 + h * w * (c1 + c2))), kind="fuse")
+
+
+def _spp_fill(plan, i, L, op):
+    _carried(plan, i, L, op, L["ch"], 4 * L["ch"], 5, 1, 4 * L["ch"])
+
+
+def _spp_row(L, es):  # comparisons only: x once, the four slices once
+    n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
+    return dict(name="spp %d k5,9,13 @%dx%d" % (ch, h, w), flops=0.0, bytes=float(es * n * h * w * 5 * ch), kind="fuse")
+
+
+def _xpair_out(L):
+    return (L["pack2"].cout,) + _out_hw(L["h"], L["w"], 3, 2)
+
+
+def _xpair_fill(plan, i, L, op):
+    fill_xpair_desc(op.xpair, plan._ptr(L["x"], plan.patches, i, "xpair.x"), plan.arena.ptr(L["y"]), L["n"], L["h"],
+                    L["w"], L["pack"], L["pack2"], plan.dtype_code)
+
+
+def _xpair_row(L, es):
+    pk, n, h, w = _pnhw(L)
+    p2 = L["pack2"]
+    _, ho, wo = _xpair_out(L)
+    macs = n * (h * w * pk.cin * pk.cout + ho * wo * 9 * p2.cin * p2.cout)
+    byt = es * (n * (h * w * pk.cin + ho * wo * p2.cout) + pk.cin * pk.cout + 9 * p2.cin * p2.cout)
+    return dict(name="extra %d>%d>%d k1,k3s2 @%dx%d" % (pk.cin, pk.cout, p2.cout, h, w), flops=2.0 * macs,
+                bytes=float(byt), kind="conv")
+
+
+def _dkres_fill(plan, i, L, op):  # carried by the op's ssdk_xpair_desc (include/ssdk.h SSDK_OP_DKRES)
+    fill_dkres_desc(op.xpair, plan._ptr(L["x"], plan.patches, i, "xpair.x"), plan.arena.ptr(L["y"]), L["n"], L["h"],
+                    L["w"], L["pack"], L["pack2"], plan.dtype_code)
+
+
+def _dkres_row(L, es):  # both convolutions' MACs; x in and y out once (mid never leaves the CU), the weights
+    pk, n, h, w = _pnhw(L)
+    p2 = L["pack2"]
+    macs = n * h * w * (pk.cin * pk.cout + 9 * p2.cin * p2.cout)
+    byt = es * (n * h * w * (pk.cin + p2.cout) + pk.cin * pk.cout + 9 * p2.cin * p2.cout)
+    return dict(name="dkres %d>%d>%d k1,k3 @%dx%d" % (pk.cin, pk.cout, p2.cout, h, w), flops=2.0 * macs,
+                bytes=float(byt), kind="conv")
+
+
+def _dense_fill(plan, i, L, op):  # carried by the op's ssdk_xpair_desc (include/ssdk.h SSDK_OP_DENSE)
+    fill_dense_desc(op.xpair, plan.arena.ptr(L["x"]), L["n"], L["h"], L["w"], L["cin"], L["ld"], L["pack"], plan.dtype_code,
+                    plan.es)
+
+
+def _dense_row(L, es):  # both convolutions' MACs; Cin channels in, 32 out (m never leaves the CU), the weights
+    pk, n, h, w = _pnhw(L)
+    macs = n * h * w * (pk.cin * pk.cmid + 9 * pk.cmid * pk.cout)
+    byt = es * (n * h * w * (pk.cin + pk.cout) + pk.cin * pk.cmid + 9 * pk.cmid * pk.cout)
+    return dict(name="dense %d>%d>%d k1,k3 @%dx%d" % (pk.cin, pk.cmid, pk.cout, h, w), flops=2.0 * macs,
+                bytes=float(byt), kind="conv")
+
+
+def _densepool_fill(plan, i, L, op):
+    c = _carried(plan, i, L, op, L["ch"], L["ch"], 2, 2, L["ld"], act="relu")
+    c.scale, c.bias = L["a"].data_ptr(), L["b"].data_ptr()
+
+
+def _densepool_out(L):
+    return (L["ch"], L["h"] // 2, L["w"] // 2)
+
+
+def _densepool_row(L, es):  # the block's c channels in, a quarter of the pixels out
+    n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
+    _, ho, wo = _densepool_out(L)
+    return dict(name="densepool %d @%dx%d" % (ch, h, w), flops=16.0 * n * ch * ho * wo,
+                bytes=float(es * n * ch * (h * w + ho * wo) + 8 * ch), kind="pool")
+
+
+def _denseplace_fill(plan, i, L, op):
+    _carried(plan, i, L, op, L["ch"], L["ch"], 1, 1, L["ld"])
+
+
+def _denseplace_row(L, es):  # data movement: the map in and out once
+    n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
+    return dict(name="denseplace %d>%d @%dx%d" % (ch, L["ld"], h, w), flops=0.0, bytes=float(es * 2 * n * ch * h * w), kind="fuse")
+
+
+def _shuffle_fill(plan, i, L, op):  # carried by the op's mb (+ xpair) members (include/ssdk.h SSDK_OP_SHUFFLE)
+    fill_shuffle_desc(op, plan._ptr(L["x"], plan.patches, i, "mb.x"), plan.arena.ptr(L["y"]), L["n"], L["h"], L["w"],
+                      L["pack"], plan.dtype_code, ld_in=L.get("ld", 0))
+
+
+def _shuffle_row(L, es):  # branch2's MACs; x in and y out once (neither intermediate leaves the CU), the weights
+    pk, n, h, w = _pnhw(L)
+    cb = pk.cb
+    return dict(name="shuffle %d k1,dw3,k1 @%dx%d" % (2 * cb, h, w), flops=2.0 * n * h * w * (2 * cb * cb + 9 * cb),
+                bytes=float(es * (n * h * w * 4 * cb + 2 * cb * cb + 9 * cb)), kind="conv")
+
+
+def _shuffledown_out(L):
+    return (pad8(2 * L["pack"].cb),) + _out_hw(L["h"], L["w"], 3, 2)
+
+
+def _shuffledown_row(L, es):  # both branches' MACs; x in once, y out once, the weights
+    pk, n, h, w = _pnhw(L)
+    cb, cin = pk.cb, pk.cin
+    _, ho, wo = _shuffledown_out(L)
+    macs = n * (h * w * cin * cb + ho * wo * (9 * cb + cb * cb + 9 * cin + cin * cb))
+    return dict(name="shuffledown %d>%d k1,dw3s2,k1 @%dx%d" % (cin, 2 * cb, h, w), flops=2.0 * macs,
+                bytes=float(es * (n * (h * w * cin + ho * wo * 2 * cb) + 2 * cin * cb + cb * cb + 9 * (cin + cb))), kind="conv")
+
+
+def _stem7_out(L):
+    return (L["pack"].cout,) + _out_hw(L["h"], L["w"], 7, 2)
+
+
+def _stem7_fill(plan, i, L, op):
+    fill_stem_desc(op.stem, plan._ptr(L["x"], plan.patches, i, "stem.x"), plan.arena.ptr(L["y"]), L["n"], L["h"], L["w"], 3,
+                   L["pack"], plan.dtype_code, N.NCHW)
+
+
+def _stem7_row(L, es):
+    pk, n, h, w = _pnhw(L)
+    _, ho, wo = _stem7_out(L)
+    return dict(name="stem7 3>%d @%dx%d" % (pk.cout, h, w), flops=2.0 * n * ho * wo * 147 * pk.cout,
+                bytes=float(es * n * (3 * h * w + pk.cout * ho * wo)), kind="stem")
+
+
+def _pool_out(L):
+    return (L["ch"],) + _out_hw(L["h"], L["w"], 3, 2)
+
+
+def _pool_fill(plan, i, L, op):
+    fill_pool_desc(op.pool, plan._ptr(L["x"], plan.patches, i, "pool.x"), plan.arena.ptr(L["y"]), L["n"], L["h"], L["w"], L["ch"],
+                   plan.dtype_code)
+
+
+def _pool_row(L, es):
+    n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
+    _, ho, wo = _pool_out(L)
+    return dict(name="maxpool %d @%dx%d" % (ch, h, w), flops=9.0 * n * ch * ho * wo,
+                bytes=float(es * n * ch * (h * w + ho * wo)), kind="pool")
+
+
+def _fuse_fill(plan, i, L, op):
+    a = plan._ptr(L["a"][0], plan.patches, i, "fuse.a")
+    b = plan._ptr(L["b"][0], plan.patches, i, "fuse.b")
+    c = plan._ptr(L["c"][0], plan.patches, i, "fuse.c") if L["c"] is not None else None
+    fill_fuse_desc(op.fuse, a, b, c, plan.arena.ptr(L["y"]), L["n"], L["h"], L["w_"], L["ch"], L["w"], L["mode_b"], L["mode_c"],
+                   L["b"][3:], L["c"][3:] if L["c"] is not None else None, plan.dtype_code)
+
+
+def _fuse_row(L, es):
+    n, h, w, ch = L["n"], L["h"], L["w_"], L["ch"]
+    srcs = [L["a"], L["b"]] + ([L["c"]] if L["c"] is not None else [])
+    byt = es * (sum(v[1] * v[2] * v[3] * v[4] for v in srcs) + n * ch * h * w)
+    return dict(name="fuse x%d %d @%dx%d" % (len(srcs), ch, h, w), flops=2.0 * len(srcs) * n * ch * h * w,
+                bytes=float(byt), kind="fuse")
+
+
+OP_KINDS = {
+    None: OpKind(N.OP_CONV, _conv_out, _conv_fill, _conv_row),  # a convolution or a head
+    "mb": OpKind(N.OP_MBCONV, _mb_out, _mb_fill, _mb_row),
+    "mbse": OpKind(N.OP_MBSE, _conv_out, _mbse_fill, _mbse_row),
+    "convt": OpKind(N.OP_CONVT, _convt_out, _convt_fill, _convt_row),
+    "cat": OpKind(N.OP_CAT, lambda L: (L["c1"] + L["c2"], L["h"], L["w"]), _cat_fill, _cat_row),
+    "spp": OpKind(N.OP_SPP, lambda L: (4 * L["ch"], L["h"], L["w"]), _spp_fill, _spp_row),
+    "xpair": OpKind(N.OP_XPAIR, _xpair_out, _xpair_fill, _xpair_row),
+    "dkres": OpKind(N.OP_DKRES, lambda L: (L["pack2"].cout, L["h"], L["w"]), _dkres_fill, _dkres_row),
+    "dense": OpKind(N.OP_DENSE, lambda L: (L["cin"] + L["pack"].cout, L["h"], L["w"]), _dense_fill, _dense_row),
+    "densepool": OpKind(N.OP_DENSEPOOL, _densepool_out, _densepool_fill, _densepool_row),
+    "denseplace": OpKind(N.OP_DENSEPLACE, lambda L: (L["ch"], L["h"], L["w"]), _denseplace_fill, _denseplace_row),
+    "shuffle": OpKind(N.OP_SHUFFLE, lambda L: (pad8(2 * L["pack"].cb), L["h"], L["w"]), _shuffle_fill, _shuffle_row),
+    "shuffledown": OpKind(N.OP_SHUFFLEDOWN, _shuffledown_out, _shuffle_fill, _shuffledown_row),
+    "stem7": OpKind(N.OP_STEM7, _stem7_out, _stem7_fill, _stem7_row),
+    "pool": OpKind(N.OP_POOL, _pool_out, _pool_fill, _pool_row),
+    "fuse": OpKind(N.OP_FUSE, lambda L: (L["ch"], L["h"], L["w_"]), _fuse_fill, _fuse_row),
+}
 
 
 class _Arena(object):
@@ -1532,28 +1843,34 @@ class ConvPlan(object):
             pack = pack.with_padded_output()
         if residual is not None:
             assert value_segs(residual) == ((getattr(pack, "cout_real", pack.cout), pack.cout),), (value_segs(residual), pack.cout)
-        ho, wo = _out_hw(h, w, pack.k, pack.stride)
-        out = self.arena.get(n * pack.cout * ho * wo * self.es)
-        if lane:
-            self.side_chain = True
-            self.pinned.add(out)
-            if not isinstance(buf, ExtBuf):
-                self.pinned.add(buf)
-        self.layers.append(dict(x=buf, n=n, h=h, w=w, pack=pack, act=pack.act if act is None else act, y=out,
+        out = self._record(dict(x=buf, n=n, h=h, w=w, pack=pack, act=pack.act if act is None else act,
                                 res=residual[0] if residual is not None else None, res_mode=res_mode, nchw=False,
                                 role=role, lane=lane))
+        if lane:
+            self._pin_side(buf, out[0])
         self.keep.append(pack)
-        return self._padded((out, n, pack.cout, ho, wo), getattr(pack, "cout_real", pack.cout))
+        return self._padded(out, getattr(pack, "cout_real", pack.cout))
+
+    def _record(self, L):
+        """Appends the layer dict ``L`` with a fresh arena buffer ``y`` of the shape its kind's ``out`` gives; -> the output value."""
+        c, ho, wo = OP_KINDS[L.get("kind")].out(L)
+        L["y"] = self.arena.get(L["n"] * c * ho * wo * self.es)
+        self.layers.append(L)
+        return (L["y"], L["n"], c, ho, wo)
+
+    def _pin_side(self, buf, out):
+        """A lane != 0 op runs on the executor's side stream next to the main chain: its output and its input (unless external) are
+        never handed out again inside this plan (see head())."""
+        self.side_chain = True
+        self.pinned.add(out)
+        if not isinstance(buf, ExtBuf):
+            self.pinned.add(buf)
 
     def mbconv(self, val, pk):
         buf, n, c, h, w = val
         assert c == pk.cin, (c, pk.cin)
-        hs, ws = _out_hw(h, w, 3, 2) if pk.stem else (h, w)
-        ho, wo = _out_hw(hs, ws, 3, pk.stride)
-        out = self.arena.get(n * pk.cout * ho * wo * self.es)
-        self.layers.append(dict(kind="mb", x=buf, n=n, h=h, w=w, pack=pk, y=out))
         self.keep.append(pk)
-        return (out, n, pk.cout, ho, wo)
+        return self._record(dict(kind="mb", x=buf, n=n, h=h, w=w, pack=pk))
 
     def mbse(self, val, pack, residual=None):
         """The tail of an EfficientNet MBConv block (``MbSePack``) on ``val`` = the expanded tensor (or the block input of an
@@ -1561,31 +1878,29 @@ class ConvPlan(object):
         arena scratch, handed back as soon as the op is recorded (lane 0 ops run in order)."""
         buf, n, c, h, w = val
         assert c == pack.cin, (c, pack.cin)
-        ho, wo = _out_hw(h, w, pack.k, pack.stride)
+        L = dict(kind="mbse", x=buf, n=n, h=h, w=w, pack=pack, res=residual[0] if residual is not None else None)
+        out = self._record(L)
+        ho, wo = out[3:]
         if residual is not None:
-            assert tuple(residual[1:]) == (n, pack.cout, ho, wo), (residual[1:], (n, pack.cout, ho, wo))
-        out = self.arena.get(n * pack.cout * ho * wo * self.es)
+            assert tuple(residual[1:]) == out[1:], (residual[1:], out[1:])
         tiles = mbse_pool_tiles(h, w, pack.k, pack.stride)
         scratch = [self.arena.get(n * c * ho * wo * self.es), self.arena.get(n * tiles * c * 4), self.arena.get(n * c * 4)]
-        self.layers.append(dict(kind="mbse", x=buf, n=n, h=h, w=w, pack=pack, y=out, t=scratch[0], partial=scratch[1],
-                                gate=scratch[2], res=residual[0] if residual is not None else None))
+        L.update(t=scratch[0], partial=scratch[1], gate=scratch[2])
         for b in scratch:
             self.arena.release(b)
         self.keep.append(pack)
-        return (out, n, pack.cout, ho, wo)
+        return out
 
     def convt(self, val, pack, skip=None):
         """Transposed 3x3 / stride 2 / pad 1 convolution (``ConvTPack``) + bias (+ ``skip``, a value at the output's size): the
         decoder step of the Shelf neck as one op, [n, c, h, w] -> [n, cout, 2h - 1, 2w - 1]."""
         buf, n, c, h, w = val
         assert c == pack.cin, (c, pack.cin)
-        ho, wo = 2 * h - 1, 2 * w - 1
+        out = self._record(dict(kind="convt", x=buf, n=n, h=h, w=w, pack=pack, res=skip[0] if skip is not None else None))
         if skip is not None:
-            assert tuple(skip[1:]) == (n, pack.cout, ho, wo), (skip[1:], (n, pack.cout, ho, wo))
-        out = self.arena.get(n * pack.cout * ho * wo * self.es)
-        self.layers.append(dict(kind="convt", x=buf, n=n, h=h, w=w, pack=pack, y=out, res=skip[0] if skip is not None else None))
+            assert tuple(skip[1:]) == out[1:], (skip[1:], out[1:])
         self.keep.append(pack)
-        return (out, n, pack.cout, ho, wo)
+        return out
 
     def cat(self, a, b, up2=False):
         """Channel concatenation ``a || b`` (``up2``: ``b`` at half the size of ``a``, nearest x2 on the way) as one op
@@ -1594,9 +1909,7 @@ class ConvPlan(object):
         bbuf, nb, c2, hb, wb = b
         assert nb == n and (hb, wb) == ((h // 2, w // 2) if up2 else (h, w)) and not (up2 and (h % 2 or w % 2)), (a[1:], b[1:], up2)
         assert cat_supported(c1, c2, h, w, up2) is None, cat_supported(c1, c2, h, w, up2)
-        out = self.arena.get(n * (c1 + c2) * h * w * self.es)
-        self.layers.append(dict(kind="cat", x=buf, b=bbuf, n=n, h=h, w=w, c1=c1, c2=c2, up2=bool(up2), y=out))
-        val = (out, n, c1 + c2, h, w)
+        val = self._record(dict(kind="cat", x=buf, b=bbuf, n=n, h=h, w=w, c1=c1, c2=c2, up2=bool(up2)))
         if hasattr(a, "segs") or hasattr(b, "segs"):  # zero-padded maps keep their padding where it is: the readers' packs follow
             val = PaddedValue(val, value_segs(a) + value_segs(b))
         return val
@@ -1606,36 +1919,28 @@ class ConvPlan(object):
         [n, c, h, w] -> [n, 4 c, h, w]."""
         buf, n, c, h, w = val
         assert c >= 8 and c % 8 == 0, c
-        out = self.arena.get(n * 4 * c * h * w * self.es)
-        self.layers.append(dict(kind="spp", x=buf, n=n, h=h, w=w, ch=c, y=out))
+        out = self._record(dict(kind="spp", x=buf, n=n, h=h, w=w, ch=c))
         if hasattr(val, "segs"):  # (max-pooling keeps the zeros of a padded map where they are, in each of the four slices)
-            return PaddedValue((out, n, 4 * c, h, w), val.segs * 4)
-        return (out, n, 4 * c, h, w)
+            return PaddedValue(out, val.segs * 4)
+        return out
 
     def xpair(self, val, p1, p2, lane=0):
         buf, n, c, h, w = val
         p1 = self._fit(val, p1)
         assert c == p1.cin, (c, p1.cin)
-        ho, wo = _out_hw(h, w, 3, 2)
-        out = self.arena.get(n * p2.cout * ho * wo * self.es)
-        if lane:  # a side-stream chain op: its buffers are never handed out again (see conv())
-            self.side_chain = True
-            self.pinned.add(out)
-            if not isinstance(buf, ExtBuf):
-                self.pinned.add(buf)
-        self.layers.append(dict(kind="xpair", x=buf, n=n, h=h, w=w, pack=p1, pack2=p2, y=out, lane=lane))
+        out = self._record(dict(kind="xpair", x=buf, n=n, h=h, w=w, pack=p1, pack2=p2, lane=lane))
+        if lane:
+            self._pin_side(buf, out[0])
         self.keep.extend([p1, p2])
-        return (out, n, p2.cout, ho, wo)
+        return out
 
     def dkres(self, val, p1, p2):
         """A DarkNet residual block as one op (csrc/ssdk_dkres.hip): [n, c, h, w] -> [n, c, h, w].  The output is a buffer of its
         own -- the arena never hands out ``val``'s while ``val`` is unreleased, and the kernel refuses y == x."""
         buf, n, c, h, w = val
         assert c == p1.cin == p2.cout and p1.cout == p2.cin, (c, p1.cin, p1.cout, p2.cin, p2.cout)
-        out = self.arena.get(n * c * h * w * self.es)
-        self.layers.append(dict(kind="dkres", x=buf, n=n, h=h, w=w, pack=p1, pack2=p2, y=out))
         self.keep.extend([p1, p2])
-        return (out, n, c, h, w)
+        return self._record(dict(kind="dkres", x=buf, n=n, h=h, w=w, pack=p1, pack2=p2))
 
     def dense_block(self, n, ctot, h, w):
         """The ONE buffer [n][h][w][ctot] of a dense block (csrc/ssdk_denselayer.hip): ``dense_place`` fills its first channels,
@@ -1653,40 +1958,33 @@ class ConvPlan(object):
     def dense(self, block, n, cin, h, w, ld, pack):
         """One dense layer as one op: reads channels [0, cin) of ``block`` and writes [cin, cin + 32); returns the new count."""
         assert cin == pack.cin and cin + pack.cout <= ld, (cin, pack.cin, pack.cout, ld)
-        self.layers.append(dict(kind="dense", x=block, n=n, h=h, w=w, cin=cin, ld=ld, pack=pack, y=block))
+        L = dict(kind="dense", x=block, n=n, h=h, w=w, cin=cin, ld=ld, pack=pack, y=block)
+        self.layers.append(L)
         self.keep.append(pack)
-        return cin + pack.cout
+        return OP_KINDS["dense"].out(L)[0]
 
     def dense_pool(self, val, a, b):
         """The front of a transition on a finished block (``val``, pixel stride == channels): avgpool2x2(relu(a x + b)) as one op,
         [n, c, h, w] -> [n, c, h / 2, w / 2] dense."""
         buf, n, c, h, w = val
         assert h >= 2 and w >= 2 and a.numel() == c == b.numel(), (c, h, w, a.numel())
-        out = self.arena.get(n * c * (h // 2) * (w // 2) * self.es)
-        self.layers.append(dict(kind="densepool", x=buf, n=n, h=h, w=w, ch=c, ld=c, a=a, b=b, y=out))
         self.keep.extend([a, b])
-        return (out, n, c, h // 2, w // 2)
+        return self._record(dict(kind="densepool", x=buf, n=n, h=h, w=w, ch=c, ld=c, a=a, b=b))
 
     def shuffle_unit(self, val, pack):
         """A stride-1 ShuffleNetV2 unit as one op (csrc/ssdk_shuffle.hip): [n, Cp, h, w] -> [n, Cp, h, w], Cp = pad8(2 cb) physical
         channels of which 2 cb are real (a ``PaddedValue`` when they differ).  The output is a buffer of its own."""
         buf, n, c, h, w = val
         assert c == pad8(2 * pack.cb) and value_segs(val)[0][0] == 2 * pack.cb, (c, value_segs(val), pack.cb)
-        out = self.arena.get(n * c * h * w * self.es)
-        self.layers.append(dict(kind="shuffle", x=buf, n=n, h=h, w=w, pack=pack, y=out))
         self.keep.append(pack)
-        return self._padded((out, n, c, h, w), 2 * pack.cb)
+        return self._padded(self._record(dict(kind="shuffle", x=buf, n=n, h=h, w=w, pack=pack)), 2 * pack.cb)
 
     def shuffle_down(self, val, pack):
         """A stride-2 unit as one op: [n, ld, h, w] of which the first ``pack.cin`` channels are real -> [n, pad8(2 cb), ho, wo]."""
         buf, n, c, h, w = val
         assert c % 8 == 0 and c >= pack.cin and value_segs(val)[0][0] == pack.cin, (c, value_segs(val), pack.cin)
-        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        cp = pad8(2 * pack.cb)
-        out = self.arena.get(n * cp * ho * wo * self.es)
-        self.layers.append(dict(kind="shuffledown", x=buf, n=n, h=h, w=w, ld=c, pack=pack, y=out))
         self.keep.append(pack)
-        return self._padded((out, n, cp, ho, wo), 2 * pack.cb)
+        return self._padded(self._record(dict(kind="shuffledown", x=buf, n=n, h=h, w=w, ld=c, pack=pack)), 2 * pack.cb)
 
     @staticmethod
     def _padded(val, real):
@@ -1711,29 +2009,22 @@ class ConvPlan(object):
 
     def stem7(self, val, pack):
         buf, n, c, h, w = val
-        ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
-        out = self.arena.get(n * pack.cout * ho * wo * self.es)
-        self.layers.append(dict(kind="stem7", x=buf, n=n, h=h, w=w, pack=pack, y=out))
         self.keep.append(pack)
-        return (out, n, pack.cout, ho, wo)
+        return self._record(dict(kind="stem7", x=buf, n=n, h=h, w=w, pack=pack))
 
     def pool(self, val):
         buf, n, c, h, w = val
-        ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-        out = self.arena.get(n * c * ho * wo * self.es)
-        self.layers.append(dict(kind="pool", x=buf, n=n, h=h, w=w, ch=c, y=out))
-        return (out, n, c, ho, wo)
+        return self._record(dict(kind="pool", x=buf, n=n, h=h, w=w, ch=c))
 
     def fuse(self, a, b, c=None, weights=(1.0, 1.0, 0.0), mode_b=N.FUSE_SAME, mode_c=N.FUSE_SAME):
         """y = w0*a + w1*R_b(b) [+ w2*R_c(c)] at the resolution of ``a`` (BiFPN weighted fusion)."""
         _, n, ch, h, w = a
-        out = self.arena.get(n * ch * h * w * self.es)
-        self.layers.append(dict(kind="fuse", a=a, b=b, c=c, w=tuple(float(v) for v in weights), mode_b=mode_b,
-                                mode_c=mode_c, n=n, h=h, w_=w, ch=ch, y=out))
+        out = self._record(dict(kind="fuse", a=a, b=b, c=c, w=tuple(float(v) for v in weights), mode_b=mode_b,
+                                mode_c=mode_c, n=n, h=h, w_=w, ch=ch))
         if hasattr(a, "segs"):  # (a weighted sum of maps padded alike is padded alike)
             assert all(value_segs(v) == a.segs for v in (b, c) if v is not None), [value_segs(v) for v in (a, b, c) if v is not None]
-            return PaddedValue((out, n, ch, h, w), a.segs)
-        return (out, n, ch, h, w)
+            return PaddedValue(out, a.segs)
+        return out
 
     def head(self, val, pack, split=None, act="none", act2=None, tag="both", lane=None, position=None, level=None):
         """An NCHW output of the plan: loc|conf of one SSD level as one split GEMM (``tag='both'``) or the last
@@ -1742,7 +2033,7 @@ class ConvPlan(object):
         buf, n, c, h, w = val
         pack = self._fit(val, pack)
         assert c == pack.cin, (c, pack.cin)
-        ho, wo = _out_hw(h, w, pack.k, pack.stride)
+        _, ho, wo = OP_KINDS[None].out(dict(pack=pack, h=h, w=w))
         # small heads are leaves of latency-bound work: they run on the executor's side stream next to the main
         # chain (SSDK_SIDE_STREAM); the big levels fill the chip on their own and stay in line.  A side-lane op
         # reads its input while the main lane keeps going, so that buffer must never be handed out again inside
@@ -1793,234 +2084,17 @@ class ConvPlan(object):
         self.ws = torch.zeros(2 * need + 512, dtype=torch.uint8, device=self.device) if need else None
         self.ops = (N.Op * len(self.layers))()
         self.patches = []  # (op index, field name, external input index)
-        for i, L in enumerate(self.layers):
-            op = self.ops[i]
-            kind = L.get("kind")
-            if kind == "mb":
-                op.kind = N.OP_MBCONV
-                fill_mb_desc(op.mb, self._ptr(L["x"], self.patches, i, "mb.x"), self.arena.ptr(L["y"]), L["n"], L["h"],
-                             L["w"], L["pack"], self.dtype_code)
-                continue
-            if kind == "mbse":
-                op.kind = N.OP_MBSE
-                fill_mbse_desc(op.mbse, L["pack"], L["n"], L["h"], L["w"], self.dtype_code,
-                               self._ptr(L["x"], self.patches, i, "mbse.x"), self.arena.ptr(L["t"]), self.arena.ptr(L["partial"]),
-                               self.arena.ptr(L["gate"]), self.arena.ptr(L["y"]),
-                               self._ptr(L["res"], self.patches, i, "mbse.residual") if L["res"] is not None else None)
-                continue
-            if kind == "convt":  # carried by the op's ssdk_conv_desc (include/ssdk.h SSDK_OP_CONVT): w = the parity images
-                op.kind = N.OP_CONVT
-                c, pk = op.conv, L["pack"]
-                c.x, c.w, c.y = self._ptr(L["x"], self.patches, i, "conv.x"), pk.w.data_ptr(), self.arena.ptr(L["y"])
-                c.bias = pk.bias.data_ptr() if pk.bias is not None else None
-                c.residual = self._ptr(L["res"], self.patches, i, "conv.residual") if L["res"] is not None else None
-                c.N, c.Cin, c.H, c.W, c.Cout, c.k, c.stride, c.groups = L["n"], pk.cin, L["h"], L["w"], pk.cout, 3, 2, 1
-                c.act = c.act2 = N.ACT["none"]
-                c.split, c.dtype, c.in_layout, c.out_layout = pk.cout, self.dtype_code, N.NHWC, N.NHWC
-                continue
-            if kind in ("cat", "spp"):  # carried by the op's ssdk_conv_desc (include/ssdk.h SSDK_OP_CAT / SSDK_OP_SPP)
-                c = op.conv
-                c.x, c.y = self._ptr(L["x"], self.patches, i, "conv.x"), self.arena.ptr(L["y"])
-                if kind == "cat":
-                    op.kind = N.OP_CAT
-                    c.residual = self._ptr(L["b"], self.patches, i, "conv.residual")
-                    c.Cin, c.Cout, c.k, c.res_mode = L["c1"], L["c1"] + L["c2"], 1, 1 if L["up2"] else 0
-                else:
-                    op.kind = N.OP_SPP
-                    c.Cin, c.Cout, c.k = L["ch"], 4 * L["ch"], 5
-                c.N, c.H, c.W, c.stride, c.groups = L["n"], L["h"], L["w"], 1, 1
-                c.act = c.act2 = N.ACT["none"]
-                c.split, c.dtype, c.in_layout, c.out_layout = c.Cout, self.dtype_code, N.NHWC, N.NHWC
-                continue
-            if kind == "xpair":
-                op.kind = N.OP_XPAIR
-                op.lane = L.get("lane", 0)
-                fill_xpair_desc(op.xpair, self._ptr(L["x"], self.patches, i, "xpair.x"), self.arena.ptr(L["y"]), L["n"], L["h"],
-                                L["w"], L["pack"], L["pack2"], self.dtype_code)
-                continue
-            if kind == "dkres":  # carried by the op's ssdk_xpair_desc (include/ssdk.h SSDK_OP_DKRES)
-                op.kind = N.OP_DKRES
-                fill_dkres_desc(op.xpair, self._ptr(L["x"], self.patches, i, "xpair.x"), self.arena.ptr(L["y"]), L["n"], L["h"],
-                                L["w"], L["pack"], L["pack2"], self.dtype_code)
-                continue
-            if kind in ("shuffle", "shuffledown"):  # carried by the op's mb (+ xpair) members (include/ssdk.h SSDK_OP_SHUFFLE)
-                op.kind = N.OP_SHUFFLE if kind == "shuffle" else N.OP_SHUFFLEDOWN
-                fill_shuffle_desc(op, self._ptr(L["x"], self.patches, i, "mb.x"), self.arena.ptr(L["y"]), L["n"], L["h"], L["w"],
-                                  L["pack"], self.dtype_code, ld_in=L.get("ld", 0))
-                continue
-            if kind == "dense":  # carried by the op's ssdk_xpair_desc (include/ssdk.h SSDK_OP_DENSE)
-                op.kind = N.OP_DENSE
-                fill_dense_desc(op.xpair, self.arena.ptr(L["x"]), L["n"], L["h"], L["w"], L["cin"], L["ld"], L["pack"], self.dtype_code,
-                                self.es)
-                continue
-            if kind in ("densepool", "denseplace"):  # carried by the op's ssdk_conv_desc (include/ssdk.h)
-                c = op.conv
-                c.x, c.y = self._ptr(L["x"], self.patches, i, "conv.x"), self.arena.ptr(L["y"])
-                c.N, c.Cin, c.H, c.W, c.Cout, c.groups = L["n"], L["ch"], L["h"], L["w"], L["ch"], 1
-                c.split, c.dtype, c.in_layout, c.out_layout = L["ld"], self.dtype_code, N.NHWC, N.NHWC
-                if kind == "densepool":
-                    op.kind = N.OP_DENSEPOOL
-                    c.scale, c.bias, c.k, c.stride, c.act = L["a"].data_ptr(), L["b"].data_ptr(), 2, 2, N.ACT["relu"]
-                else:
-                    op.kind = N.OP_DENSEPLACE
-                    c.k, c.stride, c.act = 1, 1, N.ACT["none"]
-                c.act2 = N.ACT["none"]
-                continue
-            if kind == "stem7":
-                op.kind = N.OP_STEM7
-                st, pk = op.stem, L["pack"]
-                st.x = self._ptr(L["x"], self.patches, i, "stem.x")
-                st.w, st.scale, st.bias, st.y = pk.w.data_ptr(), pk.scale.data_ptr(), pk.bias.data_ptr(), self.arena.ptr(L["y"])
-                st.N, st.H, st.W, st.Cin, st.Cout = L["n"], L["h"], L["w"], 3, pk.cout
-                st.act, st.dtype, st.in_layout = N.ACT[pk.act], self.dtype_code, N.NCHW
-                continue
-            if kind == "pool":
-                op.kind = N.OP_POOL
-                pl = op.pool
-                pl.x, pl.y = self._ptr(L["x"], self.patches, i, "pool.x"), self.arena.ptr(L["y"])
-                pl.N, pl.H, pl.W, pl.C, pl.dtype = L["n"], L["h"], L["w"], L["ch"], self.dtype_code
-                continue
-            if kind == "fuse":
-                op.kind = N.OP_FUSE
-                f = op.fuse
-                f.a = self._ptr(L["a"][0], self.patches, i, "fuse.a")
-                f.b = self._ptr(L["b"][0], self.patches, i, "fuse.b")
-                f.c = self._ptr(L["c"][0], self.patches, i, "fuse.c") if L["c"] is not None else None
-                f.y = self.arena.ptr(L["y"])
-                f.w0, f.w1, f.w2 = L["w"]
-                f.mode_b, f.mode_c = L["mode_b"], L["mode_c"]
-                f.N, f.H, f.W, f.C = L["n"], L["h"], L["w_"], L["ch"]
-                f.hb, f.wb = L["b"][3], L["b"][4]
-                if L["c"] is not None:
-                    f.hc, f.wc = L["c"][3], L["c"][4]
-                f.dtype = self.dtype_code
-                continue
-            op.kind = N.OP_CONV
-            op.lane = L.get("lane", 0)  # side stream for the small heads, decided (and its input pinned) in head()
-            y_ptr = self.arena.ptr(L["y"]) if L["y"] is not None else 0
-            res_ptr = self._ptr(L["res"], self.patches, i, "conv.residual") if L["res"] is not None else None
-            fill_desc(op.conv, self._ptr(L["x"], self.patches, i, "conv.x"), L["n"], L["h"], L["w"], L["pack"],
-                      self.dtype_code, L["act"], y_ptr, N.NHWC, N.NCHW if L["nchw"] else N.NHWC, res_ptr, None,
-                      L.get("split"), L.get("act2"))
-            op.conv.res_mode = L.get("res_mode", 0)
+        for i, (L, op) in enumerate(zip(self.layers, self.ops)):
+            kind = OP_KINDS[L.get("kind")]
+            op.kind = kind.code
+            op.lane = L.get("lane", 0)  # side stream for the small heads and the small levels' chains (head(), _pin_side())
+            kind.fill(self, i, L, op)
         return self
 
     def layer_table(self):
         """Geometry of every op of the plan: dicts with name, flops (2*MAC) and algorithmic HBM bytes
         (input + output + weights, each once) -- what the per-layer roofline numbers are computed from."""
-        rows = []
-        for L in self.layers:
-            es = self.es
-            if L.get("kind") == "stem7":
-                pk, n, h, w = L["pack"], L["n"], L["h"], L["w"]
-                ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
-                rows.append(dict(name="stem7 3>%d @%dx%d" % (pk.cout, h, w), flops=2.0 * n * ho * wo * 147 * pk.cout,
-                                 bytes=float(es * n * (3 * h * w + pk.cout * ho * wo)), kind="stem"))
-                continue
-            if L.get("kind") == "pool":
-                n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
-                ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-                rows.append(dict(name="maxpool %d @%dx%d" % (ch, h, w), flops=9.0 * n * ch * ho * wo,
-                                 bytes=float(es * n * ch * (h * w + ho * wo)), kind="pool"))
-                continue
-            if L.get("kind") == "fuse":
-                n, h, w, ch = L["n"], L["h"], L["w_"], L["ch"]
-                srcs = [L["a"], L["b"]] + ([L["c"]] if L["c"] is not None else [])
-                byt = es * (sum(v[1] * v[2] * v[3] * v[4] for v in srcs) + n * ch * h * w)
-                rows.append(dict(name="fuse x%d %d @%dx%d" % (len(srcs), ch, h, w), flops=2.0 * len(srcs) * n * ch * h * w,
-                                 bytes=float(byt), kind="fuse"))
-                continue
-            if L.get("kind") == "cat":  # data movement: both sources and the output once
-                n, h, w, c1, c2 = L["n"], L["h"], L["w"], L["c1"], L["c2"]
-                src_b = (h // 2) * (w // 2) if L["up2"] else h * w
-                rows.append(dict(name="cat %d+%d%s @%dx%d" % (c1, c2, " up2" if L["up2"] else "", h, w), flops=0.0,
-                                 bytes=float(es * n * (h * w * c1 + src_b * c2 + h * w * (c1 + c2))), kind="fuse"))
-                continue
-            if L.get("kind") == "spp":  # comparisons only: x once, the four slices once
-                n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
-                rows.append(dict(name="spp %d k5,9,13 @%dx%d" % (ch, h, w), flops=0.0, bytes=float(es * n * h * w * 5 * ch),
-                                 kind="fuse"))
-                continue
-            if L.get("kind") == "densepool":  # the block's c channels in, a quarter of the pixels out
-                n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
-                rows.append(dict(name="densepool %d @%dx%d" % (ch, h, w), flops=16.0 * n * ch * (h // 2) * (w // 2),
-                                 bytes=float(es * n * ch * (h * w + (h // 2) * (w // 2)) + 8 * ch), kind="pool"))
-                continue
-            if L.get("kind") == "denseplace":  # data movement: the map in and out once
-                n, h, w, ch = L["n"], L["h"], L["w"], L["ch"]
-                rows.append(dict(name="denseplace %d>%d @%dx%d" % (ch, L["ld"], h, w), flops=0.0, bytes=float(es * 2 * n * ch * h * w),
-                                 kind="fuse"))
-                continue
-            pk, n, h, w = L["pack"], L["n"], L["h"], L["w"]
-            if L.get("kind") == "dense":  # both convolutions' MACs; Cin channels in, 32 out (m never leaves the CU), the weights
-                macs = n * h * w * (pk.cin * pk.cmid + 9 * pk.cmid * pk.cout)
-                byt = es * (n * h * w * (pk.cin + pk.cout) + pk.cin * pk.cmid + 9 * pk.cmid * pk.cout)
-                rows.append(dict(name="dense %d>%d>%d k1,k3 @%dx%d" % (pk.cin, pk.cmid, pk.cout, h, w), flops=2.0 * macs,
-                                 bytes=float(byt), kind="conv"))
-                continue
-            if L.get("kind") == "shuffle":  # branch2's MACs; x in and y out once (neither intermediate leaves the CU), the weights
-                cb = pk.cb
-                rows.append(dict(name="shuffle %d k1,dw3,k1 @%dx%d" % (2 * cb, h, w), flops=2.0 * n * h * w * (2 * cb * cb + 9 * cb),
-                                 bytes=float(es * (n * h * w * 4 * cb + 2 * cb * cb + 9 * cb)), kind="conv"))
-                continue
-            if L.get("kind") == "shuffledown":  # both branches' MACs; x in once, y out once, the weights
-                cb, cin = pk.cb, pk.cin
-                ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-                macs = n * (h * w * cin * cb + ho * wo * (9 * cb + cb * cb + 9 * cin + cin * cb))
-                rows.append(dict(name="shuffledown %d>%d k1,dw3s2,k1 @%dx%d" % (cin, 2 * cb, h, w), flops=2.0 * macs,
-                                 bytes=float(es * (n * (h * w * cin + ho * wo * 2 * cb) + 2 * cin * cb + cb * cb + 9 * (cin + cb))),
-                                 kind="conv"))
-                continue
-            if L.get("kind") == "mbse":  # depthwise + SE + gated projection: x in, y out, t written and read once, the weights
-                ho, wo = _out_hw(h, w, pk.k, pk.stride)
-                macs = n * (ho * wo * pk.k * pk.k * pk.cin + 2 * pk.cin * pk.r + ho * wo * pk.cin * pk.cout)
-                byt = (es * (n * (h * w * pk.cin + 2 * ho * wo * pk.cin + ho * wo * pk.cout) + pk.k * pk.k * pk.cin
-                             + pk.cin * pk.cout) + 4 * (2 * pk.cin * pk.r + pk.r + pk.cin))
-                rows.append(dict(name="mbse %d>%d k%d s%d @%dx%d" % (pk.cin, pk.cout, pk.k, pk.stride, h, w), flops=2.0 * macs,
-                                 bytes=float(byt), kind="mbconv"))
-                continue
-            if L.get("kind") == "convt":  # 9 taps per 2 x 2 output quad, less the last row / column's; x, skip, y and the weights once
-                macs = n * pk.cin * pk.cout * (h * w + 2 * h * (w - 1) + 2 * (h - 1) * w + 4 * (h - 1) * (w - 1))
-                ho, wo = 2 * h - 1, 2 * w - 1
-                byt = es * (n * (h * w * pk.cin + (2 if L["res"] is not None else 1) * ho * wo * pk.cout) + 9 * pk.cin * pk.cout)
-                rows.append(dict(name="convt %d>%d k3 s2 @%dx%d" % (pk.cin, pk.cout, h, w), flops=2.0 * macs, bytes=float(byt),
-                                 kind="conv"))
-                continue
-            if L.get("kind") == "xpair":
-                p2 = L["pack2"]
-                ho, wo = _out_hw(h, w, 3, 2)
-                macs = n * (h * w * pk.cin * pk.cout + ho * wo * 9 * p2.cin * p2.cout)
-                byt = es * (n * (h * w * pk.cin + ho * wo * p2.cout) + pk.cin * pk.cout + 9 * p2.cin * p2.cout)
-                rows.append(dict(name="extra %d>%d>%d k1,k3s2 @%dx%d" % (pk.cin, pk.cout, p2.cout, h, w), flops=2.0 * macs,
-                                 bytes=float(byt), kind="conv"))
-                continue
-            if L.get("kind") == "dkres":  # both convolutions' MACs; x in and y out once (mid never leaves the CU), the weights
-                p2 = L["pack2"]
-                macs = n * h * w * (pk.cin * pk.cout + 9 * p2.cin * p2.cout)
-                byt = es * (n * h * w * (pk.cin + p2.cout) + pk.cin * pk.cout + 9 * p2.cin * p2.cout)
-                rows.append(dict(name="dkres %d>%d>%d k1,k3 @%dx%d" % (pk.cin, pk.cout, p2.cout, h, w), flops=2.0 * macs,
-                                 bytes=float(byt), kind="conv"))
-                continue
-            if L.get("kind") == "mb":
-                hs, ws = _out_hw(h, w, 3, 2) if pk.stem else (h, w)
-                ho, wo = _out_hw(hs, ws, 3, pk.stride)
-                if pk.stem:  # stem 3x3/s2 (cin -> chid) + depthwise + projection
-                    macs = n * (hs * ws * 9 * pk.cin * pk.chid + ho * wo * 9 * pk.chid + ho * wo * pk.chid * pk.cout)
-                else:
-                    macs = n * (h * w * pk.cin * pk.chid + ho * wo * 9 * pk.chid + ho * wo * pk.chid * pk.cout)
-                byt = es * n * (h * w * pk.cin + ho * wo * pk.cout)
-                name = "mbconv%s %d>%d>%d s%d @%dx%d" % ("+stem" if pk.stem else "", pk.cin, pk.chid, pk.cout,
-                                                         pk.stride, h, w)
-                rows.append(dict(name=name, flops=2.0 * macs, bytes=float(byt), kind="mbconv"))
-                continue
-            ho, wo = _out_hw(h, w, pk.k, pk.stride)
-            macs = n * ho * wo * pk.cout * (pk.cin // pk.groups) * pk.k * pk.k
-            byt = es * (n * (h * w * pk.cin + ho * wo * pk.cout) + pk.cout * (pk.cin // pk.groups) * pk.k * pk.k)
-            kind = "head" if L["nchw"] else ("tower" if L.get("role") == "tower" else
-                                             ("dw" if pk.kind == "dw" else ("gconv" if pk.groups > 1 else "conv")))
-            rows.append(dict(name="%s %d>%d k%d s%d @%dx%d" % (kind, pk.cin, pk.cout, pk.k, pk.stride, h, w),
-                             flops=2.0 * macs, bytes=float(byt), kind=kind))
-        return rows
+        return [OP_KINDS[L.get("kind")].row(L, self.es) for L in self.layers]
 
     def _set_field(self, op_index, field, ptr):
         sub, name = field.split(".")
