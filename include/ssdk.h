@@ -308,7 +308,10 @@ typedef struct ssdk_conv_desc {
   int32_t dtype;        /* SSDK_BF16 | SSDK_F16 (input, weights and output) */
   int32_t in_layout, out_layout;
   int32_t res_mode;     /* bit 0: `residual` is half resolution [N][H/2][W/2][Cout], added nearest-x2-upsampled (FPN
-                           top-down path, fpn.py:80-87); bit 1: activation applied AFTER the add (ResNet blocks) */
+                           top-down path, fpn.py:80-87); bit 1: activation applied AFTER the add (ResNet blocks);
+                           bits 8-11: dilation - 1 of a 3x3 / stride-1 convolution with padding = dilation (0: dilation 1, every
+                           descriptor without them; the BasicRFB extras: include/ssdk_dconv.h names the shift and the mask and
+                           states what such a descriptor may hold -- ssdk_conv hands it to ssdk_dconv3x3) */
   const void* w_frag;   /* optional (NULL: not given): the same weights in FRAGMENT-MAJOR order, see ssdk_weight_frag_bytes.
                            Kernels that stream weights straight into MFMA operand registers (small maps: the weights ARE the
                            traffic) read it instead of `w`: 1 KiB contiguous per wave instruction instead of 16 rows x 64 B,

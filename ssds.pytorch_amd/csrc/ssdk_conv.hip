@@ -29,6 +29,7 @@
 #include "../../include/ssdk_convt.h"
 #include "../../include/ssdk_cat.h"
 #include "../../include/ssdk_dkres.h"
+#include "../../include/ssdk_dconv.h"
 #include "../../include/ssdk_denselayer.h"
 #include "../../include/ssdk_shuffle.h"
 
@@ -1082,6 +1083,9 @@ extern "C" size_t ssdk_weight_frag_bytes(int rows, int K) {
 
 extern "C" int ssdk_conv(const ssdk_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  // res_mode bits 8-11 = dilation - 1 (include/ssdk_dconv.h): a dilated layer has a kernel and checks of its own, and no kernel
+  // below ever sees a descriptor with those bits set
+  if (d && (d->res_mode & SSDK_CONV_DILATION_MASK)) return ssdk_dconv3x3(d, stream_);
   ssdk::lds_poison(stream);
   if (!d || !d->x || !d->w || !d->bias || !d->y) {
     set_error("conv: null pointer (x, w, bias and y are mandatory)");
@@ -1225,7 +1229,7 @@ extern "C" int ssdk_conv(const ssdk_conv_desc* d, void* workspace, size_t worksp
   p.KT = d->k * d->k * p.cin_chunks;
   p.act = d->act;
   p.act2 = d->act2;
-  p.res_mode = d->residual ? d->res_mode : 0;
+  p.res_mode = d->residual ? (d->res_mode & 3) : 0;
   p.post = SSDK_ACT_NONE;
   if (d->residual && (d->res_mode & 2)) {  // y = act(conv + residual): the staged value is linear
     if (d->act != SSDK_ACT_NONE && d->act != SSDK_ACT_RELU && d->act != SSDK_ACT_RELU6) {
@@ -1429,6 +1433,7 @@ static int edge(hipStream_t from, hipEvent_t e, hipStream_t to) {  // work recor
 // not a member and goes through ssdk_conv, with its checks and error messages, as before.
 static bool group_member_params(const ssdk_conv_desc* d, ConvParams* p) {
   if (!d->x || !d->w || !d->w_frag || !d->bias || !d->y || d->residual) return false;
+  if (d->res_mode & SSDK_CONV_DILATION_MASK) return false;  // a dilated layer is no plain 3x3: ssdk_conv -> ssdk_dconv3x3
   if ((d->dtype != SSDK_BF16 && d->dtype != SSDK_F16) || d->k != 3 || d->stride != 1 || d->groups != 1) return false;
   if (d->N < 1 || d->Cin < 8 || (d->Cin % 8) || d->H < 1 || d->W < 1 || d->Cout < 1 || d->in_layout != LAYOUT_NHWC) return false;
   if (((uintptr_t)d->x | (uintptr_t)d->w | (uintptr_t)d->w_frag | (uintptr_t)d->y | (uintptr_t)d->y2) & 15) return false;

@@ -150,6 +150,7 @@ _HEADERS = (
     ("ssdk_convt.h", {"ssdk_convt_desc": "ConvTDesc"}),  # the transposed convolution of the Shelf neck
     ("ssdk_cat.h", {"ssdk_cat_desc": "CatDesc", "ssdk_spp_desc": "SppDesc"}),  # channel concatenation and SPP block of the YOLO necks
     ("ssdk_dkres.h", {"ssdk_dkres_desc": "DkresDesc"}),  # the DarkNet residual block as one launch
+    ("ssdk_dconv.h", {}),  # the dilated 3x3 convolution of the RFB extras (described by ssdk_conv_desc: no descriptor of its own)
     # the DenseNet dense layer as one launch, the front of a transition and the copy into a block's buffer
     ("ssdk_denselayer.h", {"ssdk_dense_layer_desc": "DenseLayerDesc", "ssdk_dense_pool_desc": "DensePoolDesc",
                            "ssdk_dense_place_desc": "DensePlaceDesc"}),
@@ -177,9 +178,9 @@ for _path, (_name, _mirrors) in zip(_PATHS, _HEADERS):
 _K = _ABI.constants
 
 ABI_VERSION = _K["SSDK_VERSION"]  # a library of an older version is refused by _load
-(EXPORTS, CONVT_EXPORTS, CAT_EXPORTS, DKRES_EXPORTS, DENSE_EXPORTS, SHUFFLE_EXPORTS, CATTRAIN_EXPORTS,
+(EXPORTS, CONVT_EXPORTS, CAT_EXPORTS, DKRES_EXPORTS, DCONV_EXPORTS, DENSE_EXPORTS, SHUFFLE_EXPORTS, CATTRAIN_EXPORTS,
  CONVTTRAIN_EXPORTS) = (tuple(_h.functions) for _h in _PARSED)
-(_, CONVT_HEADER_PATH, CAT_HEADER_PATH, DKRES_HEADER_PATH, DENSE_HEADER_PATH, SHUFFLE_HEADER_PATH, CATTRAIN_HEADER_PATH,
+(_, CONVT_HEADER_PATH, CAT_HEADER_PATH, DKRES_HEADER_PATH, DCONV_HEADER_PATH, DENSE_HEADER_PATH, SHUFFLE_HEADER_PATH, CATTRAIN_HEADER_PATH,
  CONVTTRAIN_HEADER_PATH) = _PATHS
 
 MAX_LEVELS, MAX_ANCHORS, MAX_TOPN, MAX_NDET, MAX_NMS_N, MAX_GT = (
@@ -216,6 +217,12 @@ ShuffleUnitDesc.__doc__ = ("ssdk_shuffle_unit_desc: y[2i] = x[i], y[2i + 1] = br
                            "launch, the channel shuffle in the store.")
 ShuffleDownDesc.__doc__ = "ssdk_shuffle_down_desc: y[2i] = branch1(x)[i], y[2i + 1] = branch2(x)[i] -- the stride-2 unit in one launch."
 DKRES_TILE_H, DKRES_TILE_W = _K["SSDK_DKRES_TILE_H"], _K["SSDK_DKRES_TILE_W"]  # a workgroup's output tile
+# the dilation field of ssdk_conv_desc.res_mode and the dilated kernel's tiling (include/ssdk_dconv.h)
+CONV_DILATION_SHIFT, CONV_DILATION_MASK = _K["SSDK_CONV_DILATION_SHIFT"], _K["SSDK_CONV_DILATION_MASK"]
+DCONV_TILE_PIXELS, DCONV_FRAG_COUT, DCONV_TILE_COUT, DCONV_KSPLIT = (
+    _K["SSDK_DCONV_" + n] for n in ("TILE_PIXELS", "FRAG_COUT", "TILE_COUT", "KSPLIT"))
+DCONV_MIN_DILATION, DCONV_MAX_DILATION, DCONV_MAX_CHANNELS, DCONV_MAX_SIDE = (
+    _K["SSDK_DCONV_" + n] for n in ("MIN_DILATION", "MAX_DILATION", "MAX_CHANNELS", "MAX_SIDE"))
 DENSE_TILE_H, DENSE_TILE_W = _K["SSDK_DENSE_TILE_H"], _K["SSDK_DENSE_TILE_W"]
 DENSE_CMID, DENSE_COUT = _K["SSDK_DENSE_CMID"], _K["SSDK_DENSE_COUT"]
 SHUFFLE_TILE_H, SHUFFLE_TILE_W = _K["SSDK_SHUFFLE_TILE_H"], _K["SSDK_SHUFFLE_TILE_W"]

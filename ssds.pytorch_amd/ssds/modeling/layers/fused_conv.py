@@ -149,8 +149,18 @@ def _strip_cols(w, segs):
 
 
 def conv_kind(conv):
-    """'dense' | 'dw' | 'g16' | 'gany' | 'stem' | None (None: not covered by the HIP kernels -> torch, reported)."""
+    """'dense' | 'dw' | 'g16' | 'gany' | 'stem' | 'dilated' | None (None: not covered by the HIP kernels -> torch, reported).
+    'dilated': a 3x3 / stride-1 convolution with padding == dilation == (d, d) that csrc/ssdk_dconv.hip takes (the BasicRFB extras);
+    never 'dense' -- the heads, towers, xpair and the training swaps that ask for 'dense' keep ignoring such a layer."""
     k = conv.kernel_size
+    if conv.dilation != (1, 1):
+        d = conv.dilation[0]
+        # (H and W are the planner's to check: the predicate's rule on the map is 1 <= H, W <= DCONV_MAX_SIDE)
+        if (k == (3, 3) and conv.stride == (1, 1) and conv.dilation == (d, d) and conv.padding == (d, d) and conv.groups == 1
+                and conv.padding_mode == "zeros"
+                and N.lib.ssdk_dconv3x3_supported(conv.in_channels, conv.out_channels, 1, 1, d, N.BF16)):
+            return "dilated"
+        return None
     if not (k[0] == k[1] and k[0] in (1, 3) and conv.stride[0] == conv.stride[1] and conv.stride[0] in (1, 2)
             and conv.padding == (k[0] // 2, k[0] // 2) and conv.dilation == (1, 1)
             and conv.padding_mode == "zeros"):
@@ -210,7 +220,7 @@ USE_WFRAG = os.environ.get("SSDK_WFRAG", "1") != "0"
 class ConvPack(object):
     """Weights of one fused layer in kernel layout (built once per model/dtype)."""
 
-    __slots__ = ("kind", "w", "scale", "bias", "cin", "cout", "k", "stride", "groups", "act", "_frag", "in_segs", "cout_real")
+    __slots__ = ("kind", "w", "scale", "bias", "cin", "cout", "k", "stride", "groups", "act", "_frag", "in_segs", "cout_real", "dilation")
 
     def with_input_segs(self, segs):
         """A copy of this dense pack for an input laid out as ``segs`` = ((real, physical), ...): zero weight columns at every
@@ -281,8 +291,27 @@ class ConvPack(object):
         self._frag = ((self.w.data_ptr(), self.w._version), img)
         return img
 
+    def dfrag(self):
+        """Weight image of a 'dilated' layer (csrc/ssdk_dconv.hip, include/ssdk_dconv.h): the fragment-major image of the matrix
+        [Cout][Kpad], k = tap * Cin + ci (tap = 3 ky + kx), Kpad = 32 * ceil(9 Cin / 32), zero columns behind 9 Cin and zero rows behind
+        Cout -- the k order of ``pack_grouped_frag`` for ONE group as wide as the layer.  The only weight tensor the kernel reads, so it
+        is built whatever USE_WFRAG says.  Cached like frag()."""
+        assert self.kind == "dilated", self.kind
+        cached = getattr(self, "_frag", None)
+        if cached is not None and cached[0] == (self.w.data_ptr(), self.w._version):
+            return cached[1]
+        rows, k_elems = self.cout, 9 * self.cin
+        g, ks = (rows + 15) // 16, (k_elems + 31) // 32
+        mat = self.w.new_zeros((g * 16, ks * 32))
+        mat[:rows, :k_elems] = self.w.reshape(rows, k_elems)
+        img = mat.view(g, 16, ks, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+        assert img.numel() * 2 == N.lib.ssdk_weight_frag_bytes(rows, ks * 32)
+        self._frag = ((self.w.data_ptr(), self.w._version), img)
+        return img
+
     def __init__(self, conv, bn, act, dtype, extra_cout=None):
         self._frag = None
+        self.dilation = int(conv.dilation[0])  # 1 for every kind but 'dilated'
         self.in_segs = None
         self.cout_real = conv.out_channels
         self.kind = conv_kind(conv)
@@ -1367,7 +1396,12 @@ def mbconv_native(x, pk, variant=0, y=None):
     return y
 
 
-def _out_hw(h, w, k, stride):
+def conv_res_mode(pack, res_mode=0):
+    """ssdk_conv_desc.res_mode of a layer: the caller's two bits, and bits 8-11 = dilation - 1 (include/ssdk_dconv.h)."""
+    return (res_mode & 3) | (((getattr(pack, "dilation", 1) - 1) << N.CONV_DILATION_SHIFT) & N.CONV_DILATION_MASK)
+
+
+def _out_hw(h, w, k, stride):  # (a 'dilated' layer is k 3 / stride 1 with padding = dilation: the map keeps its size, as here)
     pad = k // 2
     return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
 
@@ -1394,6 +1428,8 @@ def fill_desc(d, x_ptr, n, h, w, pack, dtype_code, act, y_ptr, in_layout=N.NHWC,
     d.x, d.w = x_ptr, pack.w.data_ptr()
     if pack.kind == "gany":  # not optional: gconv3x3_any_kernel reads nothing else
         frag = pack.gfrag()
+    elif pack.kind == "dilated":  # not optional either: dconv3x3_kernel
+        frag = pack.dfrag()
     else:
         frag = pack.frag() if wants_frag(pack, h, w, residual_ptr is not None, in_layout) else None
     d.w_frag = frag.data_ptr() if frag is not None else None
@@ -1406,6 +1442,7 @@ def fill_desc(d, x_ptr, n, h, w, pack, dtype_code, act, y_ptr, in_layout=N.NHWC,
     d.act2 = N.ACT[act2 if act2 is not None else act]
     d.split = split if split is not None else pack.cout
     d.dtype, d.in_layout, d.out_layout = dtype_code, in_layout, out_layout
+    d.res_mode = conv_res_mode(pack)
     return d
 
 
@@ -1437,7 +1474,7 @@ def conv_native(x, pack, act=None, residual=None, nchw_out=False, split=None, ac
     d = fill_desc(N.ConvDesc(), x.data_ptr(), n, h, w, pack, N.dtype_code(x), act, y.data_ptr(), in_layout,
                   N.NCHW if nchw_out else N.NHWC, residual.data_ptr() if residual is not None else None,
                   y2.data_ptr() if y2 is not None else None, split, act2)
-    d.res_mode = res_mode
+    d.res_mode = conv_res_mode(pack, res_mode)
     with torch.cuda.device(x.device):
         need = int(N.lib.ssdk_conv_workspace_bytes(n, pack.cin, h, w, pack.cout, pack.k, pack.stride, N.dtype_code(x)))
         if need:
@@ -1474,7 +1511,7 @@ def _conv_fill(plan, i, L, op):
     fill_desc(op.conv, plan._ptr(L["x"], plan.patches, i, "conv.x"), L["n"], L["h"], L["w"], L["pack"],
               plan.dtype_code, L["act"], y_ptr, N.NHWC, N.NCHW if L["nchw"] else N.NHWC, res_ptr, None,
               L.get("split"), L.get("act2"))
-    op.conv.res_mode = L.get("res_mode", 0)
+    op.conv.res_mode = conv_res_mode(L["pack"], L.get("res_mode", 0))  # (L["res_mode"] stays the 2-bit value)
 
 
 def _conv_row(L, es):
@@ -1484,7 +1521,8 @@ def _conv_row(L, es):
     byt = es * (n * (h * w * pk.cin + ho * wo * pk.cout) + pk.cout * (pk.cin // pk.groups) * pk.k * pk.k)
     kind = "head" if L["nchw"] else ("tower" if L.get("role") == "tower" else
                                      ("dw" if pk.kind == "dw" else ("gconv" if pk.groups > 1 else "conv")))
-    return dict(name="%s %d>%d k%d s%d @%dx%d" % (kind, pk.cin, pk.cout, pk.k, pk.stride, h, w),
+    dil = " d%d" % pk.dilation if getattr(pk, "dilation", 1) > 1 else ""
+    return dict(name="%s %d>%d k%d s%d%s @%dx%d" % (kind, pk.cin, pk.cout, pk.k, pk.stride, dil, h, w),
                 flops=2.0 * macs, bytes=float(byt), kind=kind)
 
 

@@ -1,7 +1,8 @@
 """String -> layer parser for the extra layers named in cfg.MODEL.FEATURE_LAYER (reference
-``ssds/modeling/layers/layers_parser.py:5-30``).  The RFB blocks ("RBF", "RBF:S") belong to the RFB
-detector family which is outside the MI355X hot path."""
+``ssds/modeling/layers/layers_parser.py:5-30``): all six strings of the reference, the RFB blocks under the reference's own
+spelling "RBF" / "RBF:S"."""
 from .basic_layers import ConvBNReLUx2, SepConvBNReLU
+from .rfb_layers import BasicRFB
 
 
 def parse_feature_layer(layer, in_channels, depth):
@@ -14,8 +15,10 @@ def parse_feature_layer(layer, in_channels, depth):
         return [ConvBNReLUx2(in_channels, depth, stride=2)]
     elif layer == "Conv":
         return [ConvBNReLUx2(in_channels, depth, stride=1)]
-    elif layer in ("RBF:S", "RBF"):
-        raise NotImplementedError("RFB extra layers are outside the MI355X hot path")
+    elif layer == "RBF:S":
+        return [BasicRFB(in_channels, depth, stride=2, scale=1.0, visual=2)]
+    elif layer == "RBF":
+        return [BasicRFB(in_channels, depth, stride=1, scale=1.0, visual=2)]
     elif isinstance(layer, int):
         return []
     else:

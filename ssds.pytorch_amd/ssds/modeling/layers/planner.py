@@ -80,6 +80,95 @@ def record_chain(plan, val, module, residual=None, keep_input=False, lane=0):
     return cur
 
 
+def dconv_enabled():
+    """SSDK_DCONV (default DCONV_DEFAULT): RFB extras on the recorded plan, their dilated 3x3 convolutions on csrc/ssdk_dconv.hip.
+    Read at recording time."""
+    return os.environ.get("SSDK_DCONV", DCONV_DEFAULT) != "0"
+
+
+DCONV_DEFAULT = "1"  # DESIGN 4.5m
+
+
+def _rfb_conv(plan, val, bc, what, residual=None, res_mode=0, scale=1.0):
+    """One ``BasicConv`` of a BasicRFB block as one plan op; PlanUnsupported, naming the layer, for what no kernel takes."""
+    conv, bn = bc.conv, bc.bn
+    kind = conv_kind(conv)
+    if kind == "dilated":
+        d = conv.dilation[0]
+        if not N.lib.ssdk_dconv3x3_supported(conv.in_channels, conv.out_channels, val[3], val[4], d, plan.dtype_code):
+            raise PlanUnsupported("{}: ssdk_dconv3x3_supported refuses Cin={} Cout={} H={} W={} dilation={} dtype={}".format(
+                what, conv.in_channels, conv.out_channels, val[3], val[4], d, plan.dtype_code))
+    elif kind != "dense":
+        raise PlanUnsupported("{}: conv not covered by the HIP kernels: {}".format(what, conv))
+    if bn is not None and not isinstance(bn, nn.BatchNorm2d):
+        raise PlanUnsupported("{}: BatchNorm2d expected behind the conv, found {}".format(what, type(bn).__name__))
+    pack = ConvPack(conv, bn, "relu" if bc.relu is not None else "none", plan.dtype)
+    if scale != 1.0:  # the block's ``out * scale`` rides in the folded BatchNorm
+        ones = pack.scale if pack.scale is not None else pack.bias.new_ones(pack.bias.shape)
+        pack.scale, pack.bias = ones * float(scale), pack.bias * float(scale)
+    return plan.conv(val, pack, residual=residual, res_mode=res_mode, act="relu" if res_mode & 2 else None)
+
+
+def record_rfb(plan, val, blk, keep_input=False):
+    """One ``BasicRFB`` block (layers/rfb_layers.py) as ten ops, all in line: branch0 (1x1, 3x3 / stride s, dilated 3x3), branch1 (1x1,
+    3x3, 3x3 / stride s, dilated 3x3), their concatenation (ssdk_cat2), the 1x1 / stride-s shortcut, and ConvLinear with the shortcut
+    as its residual, the block's ``scale`` folded into its BatchNorm and the ReLU behind the add.  Intermediates are released as
+    soon as they have been read; the input at the end unless ``keep_input``."""
+    from .rfb_layers import BasicConv, BasicRFB
+
+    name = type(blk).__name__
+    if not isinstance(blk, BasicRFB):
+        raise PlanUnsupported("block {} has no planner".format(name))
+    if not dconv_enabled():
+        raise PlanUnsupported("SSDK_DCONV=0: the RFB extras run on PyTorch-ROCm")
+    cin = blk.shortcut.conv.in_channels
+    if hasattr(val, "segs"):
+        raise PlanUnsupported("{} behind a zero-padded map of {} channels".format(name, val[2]))
+    if cin % 128:
+        # i = in_planes // 8 -> 3 (i // 2) -> 2 i are all multiples of 8 exactly when in_planes is a multiple of 128
+        raise PlanUnsupported("{} with in_planes = {}: the widths inside the block (in_planes // 8, 3 (in_planes // 16), in_planes // 4) "
+                              "are multiples of 8 only when in_planes is a multiple of 128".format(name, cin))
+    if val[2] != cin:
+        raise PlanUnsupported("{} of {} input channels behind a map of {}".format(name, cin, val[2]))
+    mods = list(blk.branch0) + list(blk.branch1) + [blk.ConvLinear, blk.shortcut]
+    if len(blk.branch0) != 3 or len(blk.branch1) != 4 or not all(isinstance(m, BasicConv) for m in mods):
+        raise PlanUnsupported("{}: branches of 3 and 4 BasicConv layers expected".format(name))
+    ends = []
+    for b, branch in enumerate((blk.branch0, blk.branch1)):
+        cur = val
+        for j, bc in enumerate(branch):
+            nxt = _rfb_conv(plan, cur, bc, "{} branch{}.{}".format(name, b, j))
+            if cur is not val:
+                plan.release(cur)
+            cur = nxt
+        ends.append(cur)
+    if tuple(ends[0][3:]) != tuple(ends[1][3:]):
+        raise PlanUnsupported("{}: branches end on maps of different sizes: {} and {}".format(name, ends[0][3:], ends[1][3:]))
+    why = cat_supported(ends[0][2], ends[1][2], ends[0][3], ends[0][4], False)
+    if why:
+        raise PlanUnsupported("{}: concatenation not covered by ssdk_cat2: {}".format(name, why))
+    both = plan.cat(ends[0], ends[1])
+    plan.release(ends[0])
+    plan.release(ends[1])
+    short = _rfb_conv(plan, val, blk.shortcut, name + " shortcut")
+    out = _rfb_conv(plan, both, blk.ConvLinear, name + " ConvLinear", residual=short, res_mode=2, scale=blk.scale)
+    plan.release(both)
+    plan.release(short)
+    if not keep_input:
+        plan.release(val)
+    return out
+
+
+def record_extra(plan, val, module, keep_input=False):
+    """One module made by ``layers_parser.parse_feature_layer``: a BasicRFB block on ``record_rfb``, everything else (the Conv-BN-ReLU
+    chains) on ``record_chain``."""
+    from .rfb_layers import BasicRFB
+
+    if isinstance(module, BasicRFB):
+        return record_rfb(plan, val, module, keep_input=keep_input)
+    return record_chain(plan, val, module, keep_input=keep_input)
+
+
 def record_mobilenet(plan, val, net, on_output=None):
     from ssds.modeling.nets.mobilenet import InvertedResidual, MobileNetEx
 
@@ -127,9 +216,14 @@ def record_mobilenet(plan, val, net, on_output=None):
 
 
 @_one_recording
-def build_ssd_plan(model, x):
-    """SSD (ssds/ssd.py) on a planned backbone (MobileNet, ResNet) -> finalized ConvPlan for inputs shaped like ``x``."""
-    plan = ConvPlan(x.device, x.dtype, x.shape)
+def build_ssd_plan(model, x, features=None):
+    """SSD (ssds/ssd.py) on a planned backbone (MobileNet, ResNet) -> finalized ConvPlan for inputs shaped like ``x``.  With
+    ``features`` (and ``x`` None) the backbone's maps are the plan's external inputs, as for the necks (``_neck_inputs``): the extras
+    and the heads alone."""
+    if features is not None:
+        plan, given = _neck_inputs(model, features, None)
+    else:
+        plan = ConvPlan(x.device, x.dtype, x.shape)
 
     def head(i, f, lane=None, position=None):
         # recorded right behind its feature map: the executor forks it onto the side stream, where it overlaps
@@ -145,7 +239,11 @@ def build_ssd_plan(model, x):
     # (Round 5 measured the mirror-image ordering -- extras chain + small heads as a side-stream run next to the two backbone-level
     #  heads -- at 60.9 / 62.4 k against 61.9 / 62.9 k img/s in line; the SSDK_SSD_TAIL_SIDE switch and its two recordings are
     #  gone in round 6: docs/HISTORY.md.)
-    if isinstance(model.backbone, MobileNetEx):
+    if features is not None:
+        feats = list(given)
+        for i, f in enumerate(feats):
+            head(i, f)
+    elif isinstance(model.backbone, MobileNetEx):
         feats = record_mobilenet(plan, plan.input_value(), model.backbone, on_output=head)
     else:
         feats = record_backbone(plan, plan.input_value(), model.backbone)
@@ -158,7 +256,7 @@ def build_ssd_plan(model, x):
     balance = os.environ.get("SSDK_HEAD_BALANCE", "1") != "0" and len(model.extras) > 1
     deferred = []
     for j, extra in enumerate(model.extras):
-        feats.append(record_chain(plan, feats[-1], extra, keep_input=True))
+        feats.append(record_extra(plan, feats[-1], extra, keep_input=True))
         if balance:
             deferred.append((len(feats) - 1, feats[-1]))
         else:
@@ -776,7 +874,7 @@ def build_shelf_plan(model, features=None, image=None):
     for pyr in model.shelf_head:
         xx = _record_shelf_pyramid(plan, pyr, xx)
     for i in range(n, len(model.transforms)):
-        xx.append(record_chain(plan, xx[-1], model.transforms[i], keep_input=True))
+        xx.append(record_extra(plan, xx[-1], model.transforms[i], keep_input=True))
     if len(xx) != len(model.loc) or len(xx) != len(model.conf):
         raise PlanUnsupported("{} levels, {} / {} heads".format(len(xx), len(model.loc), len(model.conf)))
     for i, f in enumerate(xx):
