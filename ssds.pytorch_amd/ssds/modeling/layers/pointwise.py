@@ -61,8 +61,11 @@ class _Pointwise(torch.autograd.Function):
         return gx, gw, gb
 
 
-def _native_ok(x, cin):
-    return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and cin % 8 == 0
+def _native_ok(x, cin, cout=0, any_width=False):
+    """``any_width`` (a layer marked by shuffletrain.use_native_shuffle): input widths that are no multiple of 8 go to the
+    ssdk_pws_* kernels of csrc/ssdk_shuffletrain.hip (at least 8 channels either side)."""
+    return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16)
+            and (cin % 8 == 0 or (any_width and cin >= 8 and cout >= 8))
             and os.environ.get("SSDK_PW_NATIVE", "1") != "0")
 
 
@@ -71,16 +74,40 @@ class _PointwiseNative(torch.autograd.Function):
     launch, the weight gradient comes back in fp32 without a cast) or in x's dtype; bias fp32 / 16-bit or None.
         forward          ssdk_pw_prepare (fp32 weight) + ssdk_pw_forward(a = W)
         input gradient   ssdk_pw_forward(a = W^T)
-        weight gradient  ssdk_pw_wgrad (fp32, fixed-order reduction)"""
+        weight gradient  ssdk_pw_wgrad (fp32, fixed-order reduction)
+    ``any_width`` (marked layers, at least 8 channels either side): a Cin that is no multiple of 8 runs all three on
+    ssdk_pws_prepare / _forward / _wgrad, a Cout that is none takes ssdk_pws_forward for the input gradient (csrc/ssdk_shuffletrain.hip)."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, want_sums=False):
+    def forward(ctx, x, w, bias, want_sums=False, any_width=False):
         """``want_sums``: also return sums [Cout, 2] = per-channel (sum y, sum y^2) of the stored outputs -- the batch
         statistics of the BatchNorm that follows (ssdk_pw_forward_stats: no pass over y); non-differentiable."""
         b, cin, h, wd = (int(v) for v in x.shape)
         cout, hw, dev, dt = int(w.shape[0]), h * wd, x.device, x.dtype
         code = N.dtype_code(x)
         x = x.detach()
+        padded = bool(any_width) and cin >= 8 and cout >= 8 and (cin % 8 != 0 or cout % 8 != 0)
+        if padded:  # w16 [Cout, Kp], wt16 [Cin, Mp]: rows zero-padded to a multiple of 8
+            from ssds.modeling.layers import shuffletrain as ST
+
+            with torch.cuda.device(dev):
+                w16, wt16 = ST.prepare_weights(w, dt)
+                b32 = None if bias is None else bias.detach().float().contiguous()
+                y = torch.empty((b, cout, h, wd), device=dev, dtype=dt)
+                if cin % 8 != 0 or want_sums:
+                    sums = ST.pws_forward(x.data_ptr(), cin * hw, w16, b32, y.data_ptr(), cout * hw, b, cin, cout, hw, code, dev, want_sums)
+                else:  # (Kp = Cin: w16 is the matrix ssdk_pw_forward takes)
+                    sums = None
+                    N.check(N.lib.ssdk_pw_forward(x.data_ptr(), w16.data_ptr(), None if b32 is None else b32.data_ptr(), y.data_ptr(),
+                                                  b, cin, cout, hw, code, N.stream_ptr(dev)), "pw_forward")
+            ctx.save_for_backward(x, wt16)
+            ctx.meta = (w.dtype, None if bias is None else bias.dtype)
+            ctx.cout, ctx.padded = cout, True
+            if want_sums:
+                ctx.mark_non_differentiable(sums)
+                ctx.set_materialize_grads(False)
+                return y, sums
+            return y
         with torch.cuda.device(dev):
             sp = N.stream_ptr(dev)
             if w.dtype == torch.float32:
@@ -105,6 +132,7 @@ class _PointwiseNative(torch.autograd.Function):
                                               b, cin, cout, hw, code, sp), "pw_forward")
         ctx.save_for_backward(x, wt16)
         ctx.meta = (w.dtype, None if bias is None else bias.dtype)
+        ctx.cout, ctx.padded = cout, False
         if want_sums:
             ctx.mark_non_differentiable(sums)
             ctx.set_materialize_grads(False)  # (no zero-filled gradient tensor for sums: a fill launch per layer and step)
@@ -116,9 +144,9 @@ class _PointwiseNative(torch.autograd.Function):
         x, wt16 = ctx.saved_tensors
         wdt, bdt = ctx.meta
         b, cin, h, wd = (int(v) for v in x.shape)
-        cout, hw, dev = int(wt16.shape[1]), h * wd, x.device
+        cout, hw, dev = ctx.cout, h * wd, x.device
         if gy is None:  # (only the non-differentiable statistics were used)
-            return None, None, None, None
+            return None, None, None, None, None
         gy = gy.contiguous()
         if gy.dtype != x.dtype:
             gy = gy.to(x.dtype)
@@ -126,14 +154,24 @@ class _PointwiseNative(torch.autograd.Function):
         gx = gw = gb = None
         with torch.cuda.device(dev):
             sp = N.stream_ptr(dev)
-            if ctx.needs_input_grad[0]:
+            if ctx.needs_input_grad[0] and ctx.padded and cout % 8 != 0:
+                from ssds.modeling.layers import shuffletrain as ST
+
+                gx = torch.empty_like(x)
+                ST.pws_forward(gy.data_ptr(), cout * hw, wt16, None, gx.data_ptr(), cin * hw, b, cout, cin, hw, code, dev)
+            elif ctx.needs_input_grad[0]:
                 if cout % 8 == 0:
                     gx = torch.empty_like(x)
                     N.check(N.lib.ssdk_pw_forward(gy.data_ptr(), wt16.data_ptr(), None, gx.data_ptr(), b, cout, cin, hw, code, sp),
                             "pw_forward (input gradient)")
                 else:  # (the kernel's K must be a multiple of 8; no such layer in the reference's networks)
                     gx = torch.matmul(wt16, gy.view(b, cout, hw)).view(b, cin, h, wd)
-            if ctx.needs_input_grad[1]:
+            if ctx.needs_input_grad[1] and ctx.padded and cin % 8 != 0:
+                from ssds.modeling.layers import shuffletrain as ST
+
+                gw32 = ST.pws_wgrad(gy, x.data_ptr(), cin * hw, b, cout, cin, hw, code, dev)
+                gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
+            elif ctx.needs_input_grad[1]:
                 need = int(N.lib.ssdk_pw_wgrad_workspace_bytes(b, cout, cin, hw))
                 ws = torch.empty(need, dtype=torch.uint8, device=dev)
                 gw32 = torch.empty((cout, cin, 1, 1), device=dev, dtype=torch.float32)
@@ -142,19 +180,19 @@ class _PointwiseNative(torch.autograd.Function):
                 gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
         if bdt is not None and ctx.needs_input_grad[2]:
             gb = gy.sum((0, 2, 3), dtype=torch.float32).to(bdt)
-        return gx, gw, gb, None
+        return gx, gw, gb, None, None
 
 
-def pointwise_conv(x, weight, bias=None, want_sums=False):
+def pointwise_conv(x, weight, bias=None, want_sums=False, any_width=False):
     """1x1 / stride 1 convolution of a contiguous NCHW tensor: weight [Cout,Cin,1,1], same floating dtype; differentiable.
     ``want_sums`` (16-bit HIP tensors only): the output carries ``_ssdk_bn_sums`` = [Cout, 2] (sum y, sum y^2) for the
     kernel-backed BatchNorm that follows (batchnorm.FastBatchNorm2d reads and consumes the attribute)."""
-    if _native_ok(x, int(x.shape[1])):
+    if _native_ok(x, int(x.shape[1]), int(weight.shape[0]), any_width):
         if want_sums:
-            y, sums = _PointwiseNative.apply(x, weight, bias, True)
+            y, sums = _PointwiseNative.apply(x, weight, bias, True, any_width)
             y._ssdk_bn_sums = sums
             return y
-        return _PointwiseNative.apply(x, weight, bias)
+        return _PointwiseNative.apply(x, weight, bias, False, any_width)
     if weight.dtype != x.dtype:
         weight = weight.to(x.dtype)
         bias = bias.to(x.dtype) if bias is not None else None
@@ -166,6 +204,7 @@ BN_STATS_MIN_BYTES = 64 << 20  # output tensors from 64 MiB on hand their BatchN
 
 class PointwiseConv2d(nn.Conv2d):
     _ssdk_bn_follows = False  # set by fuse_conv_bn_statistics: the next module is a kernel-backed BatchNorm in training mode
+    _ssdk_any_width = False  # set by shuffletrain.use_native_shuffle: widths that are no multiple of 8 take the ssdk_pws_* kernels
 
     def _native(self, x):
         return (x.is_cuda and x.dim() == 4 and self.kernel_size == (1, 1) and self.stride == (1, 1)
@@ -179,7 +218,7 @@ class PointwiseConv2d(nn.Conv2d):
         if torch.is_autocast_enabled():
             dt = torch.get_autocast_dtype("cuda")
             x = x.to(dt)
-            if not (_native_ok(x, self.in_channels) and w.dtype == torch.float32):
+            if not (_native_ok(x, self.in_channels, self.out_channels, self._ssdk_any_width) and w.dtype == torch.float32):
                 w = w.to(dt)  # (the native kernels take the fp32 master weights themselves: no cast launch, fp32 gradient)
                 bias = bias.to(dt) if bias is not None else None
         elif w.dtype != x.dtype:
@@ -189,7 +228,7 @@ class PointwiseConv2d(nn.Conv2d):
         want = (self._ssdk_bn_follows and self.training
                 and x.shape[0] * self.out_channels * x.shape[2] * x.shape[3] * 2 >= BN_STATS_MIN_BYTES)
         with torch.autocast("cuda", enabled=False):
-            return pointwise_conv(x, w, bias, want_sums=want)
+            return pointwise_conv(x, w, bias, want_sums=want, any_width=self._ssdk_any_width)
 
 
 def fuse_conv_bn_statistics(model):

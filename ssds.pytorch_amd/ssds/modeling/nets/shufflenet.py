@@ -12,7 +12,8 @@ A unit, with ``Cb = oup // 2``:
 ``branch1`` = dw3x3/s + BN, 1x1 + BN + ReLU; ``branch2`` = 1x1 + BN + ReLU, dw3x3/s + BN, 1x1 + BN + ReLU.
 In eval mode on a HIP device the backbone is part of the detector's recorded plan (layers/planner.py ``record_shufflenet``): every
 unit is ONE launch of csrc/ssdk_shuffle.hip that writes the interleaved result directly -- no chunk, cat or shuffle exists as an
-operation.  Training runs through this module."""
+operation.  Training runs through this module: under ``layers/shuffletrain.use_native_shuffle`` a unit's 1x1 on the channel slice,
+its depthwise 3x3 and the interleaving join run on the project's kernels, forward and backward (csrc/ssdk_shuffletrain.hip)."""
 import torch
 import torch.nn as nn
 
@@ -60,7 +61,15 @@ class InvertedResidual(nn.Module):
     def depthwise_conv(i, o, kernel_size, stride=1, padding=0, bias=False):
         return nn.Conv2d(i, o, kernel_size, stride, padding, bias=bias, groups=i)
 
+    native_shuffle = False  # set per unit by layers/shuffletrain.use_native_shuffle
+
     def forward(self, x):
+        if self.native_shuffle:
+            from ssds.modeling.layers import shuffletrain
+
+            out = shuffletrain.try_unit(self, x)  # (None: x is outside the kernels' contract)
+            if out is not None:
+                return out
         if self.stride == 1:
             x1, x2 = x.chunk(2, dim=1)
             out = torch.cat((x1, self.branch2(x2)), dim=1)

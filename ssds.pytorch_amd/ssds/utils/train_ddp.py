@@ -67,6 +67,15 @@ class Solver(object):
                 from ssds.modeling.layers.batchnorm import fuse_bn_into_depthwise
 
                 fuse_bn_into_depthwise(self.model)  # expand BN (+ ReLU6) applied by the depthwise kernels on load: no apply pass
+        from ssds.modeling.layers import shuffletrain
+        from ssds.modeling.nets.shufflenet import ShuffleNetV2
+
+        if shuffletrain.enabled() and isinstance(getattr(self.model, "backbone", None), ShuffleNetV2):
+            # ShuffleNetV2 backbones: the units' slice 1x1 and join on csrc/ssdk_shuffletrain.hip, their depthwise 3x3
+            # on the project's depthwise kernels, 1x1 layers of any width.  After the BatchNorm swap and before the two calls below,
+            # so the new DepthwiseConv2d / FastBatchNorm2d pairs get their statistics hand-off.  SSDK_SHUFFLE_TRAIN=0: chunk / cat /
+            # channel_shuffle and nn.Conv2d.  Other backbones are not touched.
+            shuffletrain.use_native_shuffle(self.model)
         if os.environ.get("SSDK_PW_GEMM", "1") != "0":
             from ssds.modeling.layers.pointwise import use_pointwise_gemm
 
