@@ -24,6 +24,9 @@ struct PwtParams {
   // SL kernels only (channel slices, ssdk_shuffletrain.hip): elements between two images of x / of y, leading dimension of a
   size_t xs, ys;
   u32 lda;
+  // AF kernels only (ssdk_densetrain.hip): coef [K][4] = (a, b, ., .) of the operand transform, byte offset of its LDS copy
+  const float* coef;
+  u32 cf_off;
 };
 
 // 8 consecutive 16-bit elements at p (any 2-byte alignment); lanes with nvalid < 8 read element by element and zero-fill
@@ -64,6 +67,40 @@ __device__ __forceinline__ void pw_transpose8(const u32x4 (&raw)[8], u32x4 (&bop
       bop[2 * h][q] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);      // low halves: pixel 2h of channels 2q, 2q + 1
       bop[2 * h + 1][q] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);  // high halves: pixel 2h + 1
     }
+  }
+}
+
+// AF: the operand transform of a dense layer's first 1x1 (ssdk_densetrain.hip): op(x) = round_DT(max(fmaf(a, x, b), 0)) with the
+// channel's (a, b) of the deferred BatchNorm -- what its apply pass would have stored, formed while the operand is staged.
+// Elements >= nvalid (outside the plane) become zero, not max(b, 0): the weight gradient contracts over pixels.
+template <int DT>
+__device__ __forceinline__ u32x4 pw_affine8(const u32x4 v, float a, float b, int nvalid) {
+  u32x4 o;
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    float lo = fmaxf(__builtin_fmaf(a, bits16_to_f32<DT>(v[h] & 0xffffu), b), 0.f);
+    float hi = fmaxf(__builtin_fmaf(a, bits16_to_f32<DT>(v[h] >> 16), b), 0.f);
+    if (2 * h >= nvalid) lo = 0.f;
+    if (2 * h + 1 >= nvalid) hi = 0.f;
+    o[h] = pack2_16<DT>(lo, hi);
+  }
+  return o;
+}
+// ... of a lane's 8 x 8 block: cf = the LDS copy [32 KS][2] of (a, b), at the block's first channel (zeros for channels >= K)
+template <int DT>
+__device__ __forceinline__ void pw_affine_raw(u32x4 (&raw)[8], const float* cf, int nvalid) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 ab = *reinterpret_cast<const f32x4*>(cf + 4 * q);  // channels 2q, 2q + 1: a lane group reads one address
+    raw[2 * q] = pw_affine8<DT>(raw[2 * q], ab[0], ab[1], nvalid);
+    raw[2 * q + 1] = pw_affine8<DT>(raw[2 * q + 1], ab[2], ab[3], nvalid);
+  }
+}
+// coef [K][4] -> its LDS copy [32 KS][2] (the caller's barrier behind it)
+__device__ __forceinline__ void pw_stage_coef(float* cf, const float* coef, u32 K, u32 KS, u32 tid) {
+  for (u32 c = tid; c < KS * 32u; c += PWT_THREADS) {
+    cf[2u * c] = c < K ? coef[4u * c] : 0.f;
+    cf[2u * c + 1u] = c < K ? coef[4u * c + 1u] : 0.f;
   }
 }
 
@@ -145,7 +182,8 @@ __device__ __forceinline__ void pw_store_frag(const f32x4 (&acc)[8], u16* yb, u3
 // ---- (E) short K (<= 96 channels): the B operands of a 128-pixel group stay in registers, the wave walks over ALL output
 // fragments of the slice.  Expansion layers (16 -> 96 ... 96 -> 576) and the input gradients of the projections. ---------------
 // SL: x and y are channel slices (own image strides), a has a leading dimension, K and M are any values >= 8
-template <int DT, int KS, bool STATS = false, bool SL = false>
+// AF: the operand is op(x) (pw_affine8), coefficients in LDS behind the fragments
+template <int DT, int KS, bool STATS = false, bool SL = false, bool AF = false>
 __global__ __launch_bounds__(PWT_THREADS) void pw_gemm_short_kernel(const PwtParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const u32 tid = threadIdx.x, lane = tid & 63u;
@@ -160,6 +198,8 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_gemm_short_kernel(const PwtPar
   if constexpr (STATS) {
     for (u32 i = lane; i < (u32)p.nf * 32u; i += 64u) wst[i] = 0.f;
   }
+  const float* cf = reinterpret_cast<const float*>(smem + p.cf_off);
+  if constexpr (AF) pw_stage_coef(reinterpret_cast<float*>(smem + p.cf_off), p.coef, K, (u32)KS, tid);
   __syncthreads();
   const u32 gstride = gridDim.x * 4u;
   for (u32 g = blockIdx.x * 4u + wave; g < p.groups; g += gstride) {
@@ -174,6 +214,7 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_gemm_short_kernel(const PwtPar
       u32x4 raw[8];
       if (tail) pw_load_raw<true, SL>(xb, HW, K, (u32)ks * 32u + fg * 8u, nvalid, raw);
       else pw_load_raw<false, SL>(xb, HW, K, (u32)ks * 32u + fg * 8u, 8, raw);
+      if constexpr (AF) pw_affine_raw<DT>(raw, cf + 2u * ((u32)ks * 32u + fg * 8u), tail ? nvalid : 8);
       pw_transpose8(raw, bop[ks]);
     }
     for (u32 f = 0; f < nf; ++f) {
@@ -221,7 +262,7 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_gemm_short_kernel(const PwtPar
 // ---- (P) long K: NF output fragments x 8 pixel sets of accumulators per wave, k-steps outermost, the weights of the slice
 // staged in chunks of PWT_KC k-steps (a workgroup's four waves walk through the chunks together).  Projection layers
 // (96 ... 960 -> 16 ... 320) and the input gradients of the expansions. -------------------------------------------------------
-template <int DT, int NF, bool STATS = false, bool SL = false>
+template <int DT, int NF, bool STATS = false, bool SL = false, bool AF = false>
 __global__ __launch_bounds__(PWT_THREADS) void pw_gemm_long_kernel(const PwtParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const u32 tid = threadIdx.x, lane = tid & 63u;
@@ -230,6 +271,11 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_gemm_long_kernel(const PwtPara
   const u32 M = (u32)p.M, K = (u32)p.K, HW = (u32)p.HW, KS = (u32)p.KS;
   const u32 m0 = blockIdx.y * (u32)(16 * NF);
   const bool one_chunk = KS <= (u32)PWT_KC;
+  const float* cf = reinterpret_cast<const float*>(smem + p.cf_off);
+  if constexpr (AF) {
+    pw_stage_coef(reinterpret_cast<float*>(smem + p.cf_off), p.coef, K, KS, tid);
+    if (!one_chunk) __syncthreads();
+  }
   if (one_chunk) {
     pw_stage_a<SL>(smem, p.a, M, K, SL ? p.lda : K, m0, (u32)NF, 0u, KS, tid);
     __syncthreads();
@@ -272,6 +318,7 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_gemm_long_kernel(const PwtPara
       }
       for (u32 ks = 0; ks < nks; ++ks) {
         u32x4 bop[8];
+        if constexpr (AF) pw_affine_raw<DT>(raw, cf + 2u * ((c0 + ks) * 32u + fg * 8u), tail ? nvalid : 8);
         pw_transpose8(raw, bop);
         const u32 kn = c0 + ks + 1u;
         if (kn < KS) {  // the next k-step's block travels under this one's MFMAs
@@ -366,10 +413,11 @@ static PwtPlan pw_gemm_plan(PwtParams& p, int B, int K, int M, int HW, bool stat
 
 // stats_ws (optional): [gx * 4 waves][M][2] fp32 per-wave moments of the stored outputs (the caller reduces them)
 // SL: xs / ys / lda as PwtParams describes them (ignored otherwise)
-template <bool SL = false>
+// AF: coef [K][4] of the operand transform (its LDS copy lies behind the plan's bytes)
+template <bool SL = false, bool AF = false>
 static int pw_gemm_launch(const void* x, const void* a, const float* bias, void* y, int B, int K, int M, int HW, int dtype,
                           hipStream_t stream, float* stats_ws = nullptr, unsigned* rows_out = nullptr, size_t xs = 0, size_t ys = 0,
-                          unsigned lda = 0) {
+                          unsigned lda = 0, const float* coef = nullptr) {
   PwtParams p;
   p.x = (const u16*)x;
   p.a = (const u16*)a;
@@ -383,14 +431,16 @@ static int pw_gemm_launch(const void* x, const void* a, const float* bias, void*
   const PwtPlan pl = pw_gemm_plan(p, B, K, M, HW, st);
   if (rows_out) *rows_out = pl.gx * 4u;
   const dim3 grid(pl.gx, (unsigned)pl.slices);
-  const size_t lds = pl.lds;
+  p.coef = coef;
+  p.cf_off = (u32)pl.lds;
+  const size_t lds = pl.lds + (AF ? (size_t)p.KS * 32 * 2 * sizeof(float) : 0);
   const int nf = pl.nf;
   if (pl.is_short) {
 #define SSDK_PWS(DT, KS_, ST_)                                                                                         \
   do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_gemm_short_kernel<DT, KS_, ST_, SL>),                     \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_gemm_short_kernel<DT, KS_, ST_, SL, AF>),                     \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
-    hipLaunchKernelGGL((pw_gemm_short_kernel<DT, KS_, ST_, SL>), grid, dim3(PWT_THREADS), lds, stream, p);                \
+    hipLaunchKernelGGL((pw_gemm_short_kernel<DT, KS_, ST_, SL, AF>), grid, dim3(PWT_THREADS), lds, stream, p);                \
   } while (0)
 #define SSDK_PWSK(DT, KS_)             \
   do {                                 \
@@ -412,9 +462,9 @@ static int pw_gemm_launch(const void* x, const void* a, const float* bias, void*
   }
 #define SSDK_PWL(DT, NF_, ST_)                                                                                        \
   do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_gemm_long_kernel<DT, NF_, ST_, SL>),                      \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_gemm_long_kernel<DT, NF_, ST_, SL, AF>),                      \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
-    hipLaunchKernelGGL((pw_gemm_long_kernel<DT, NF_, ST_, SL>), grid, dim3(PWT_THREADS), lds, stream, p);                 \
+    hipLaunchKernelGGL((pw_gemm_long_kernel<DT, NF_, ST_, SL, AF>), grid, dim3(PWT_THREADS), lds, stream, p);                 \
   } while (0)
 #define SSDK_PWLN(DT, NF_)            \
   do {                                \
@@ -448,9 +498,11 @@ struct PwgParams {
   u32 mt, nt;     // tiles of the [Cout, Cin] matrix
   u32 splits;     // pixel ranges
   u32 cps;        // chunks per split
+  const float* coef;  // AF kernels only: [Cin][4] = (a, b, ., .), x is read as op(x) (pw_affine8)
 };
 
-template <int DT, int MFW, int NFW>
+// AF: a lane's rows of x are fixed for the whole kernel, so their (a, b) live in registers
+template <int DT, int MFW, int NFW, bool AF = false>
 __global__ __launch_bounds__(PWT_THREADS) void pw_wgrad_kernel(const PwgParams p) {
   const u32 tid = threadIdx.x, lane = tid & 63u;
   const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
@@ -466,6 +518,15 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_wgrad_kernel(const PwgParams p
   for (int i = 0; i < MFW; ++i)
 #pragma unroll
     for (int j = 0; j < NFW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float ca[AF ? NFW : 1], cb[AF ? NFW : 1];
+  if constexpr (AF) {
+#pragma unroll
+    for (int j = 0; j < NFW; ++j) {
+      const u32 row = n0 + 16u * (u32)j + fr;
+      ca[j] = row < Cin ? p.coef[4u * row] : 0.f;
+      cb[j] = row < Cin ? p.coef[4u * row + 1u] : 0.f;
+    }
+  }
   const u32 c_end = min(p.chunks, (s + 1u) * p.cps);
   for (u32 c = s * p.cps; c < c_end; ++c) {
     // k-step u of the chunk = its pixels 32 u .. 32 u + 31, lane group fg the 8 pixels 32 u + 8 fg ..: ONE load instruction
@@ -493,6 +554,12 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_wgrad_kernel(const PwgParams p
         if (row < Cin) bv[j][u] = tail ? pw_load8<true>(src + 32 * u, (int)HW - (int)p0 - 32 * u) : pw_load8<false>(src + 32 * u, 8);
         else bv[j][u] = u32x4{0u, 0u, 0u, 0u};
       }
+    }
+    if constexpr (AF) {  // (rows >= Cin: a = b = 0, the zeros stay zeros)
+#pragma unroll
+      for (int j = 0; j < NFW; ++j)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) bv[j][u] = pw_affine8<DT>(bv[j][u], ca[j], cb[j], tail ? (int)HW - (int)p0 - 32 * u : 8);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
@@ -525,7 +592,7 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_wgrad_kernel(const PwgParams p
 constexpr u32 PWG_RS = 288;
 constexpr size_t PWG_LDS = 2 * 128 * PWG_RS;
 
-template <int DT>
+template <int DT, bool AF = false>
 __global__ __launch_bounds__(PWT_THREADS) void pw_wgrad_tiled_kernel(const PwgParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* la = smem;
@@ -545,9 +612,20 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_wgrad_tiled_kernel(const PwgPa
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const u32 c_begin = s * p.cps, c_end = min(p.chunks, (s + 1u) * p.cps);
   u32x4 va[8], vb[8];
+  float ca[AF ? 8 : 1], cb[AF ? 8 : 1];  // AF: (a, b) of the thread's eight staging rows of x
+  int nv = 8;                            // ... and the pixels of the fetched chunk inside the plane
+  if constexpr (AF) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const u32 rb = n0 + (u32)q * 16u + r16;
+      ca[q] = rb < Cin ? p.coef[4u * rb] : 0.f;
+      cb[q] = rb < Cin ? p.coef[4u * rb + 1u] : 0.f;
+    }
+  }
   auto fetch = [&](u32 c) {
     const u32 b = c / p.cpi, p0 = (c - b * p.cpi) * 128u + 8u * c16;
     const int nvalid = (int)HW - (int)p0;
+    nv = nvalid;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const u32 ra = m0 + (u32)q * 16u + r16, rb = n0 + (u32)q * 16u + r16;
@@ -561,6 +639,7 @@ __global__ __launch_bounds__(PWT_THREADS) void pw_wgrad_tiled_kernel(const PwgPa
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       *reinterpret_cast<u32x4*>(la + ((u32)q * 16u + r16) * PWG_RS + c16 * 16u) = va[q];
+      if constexpr (AF) vb[q] = pw_affine8<DT>(vb[q], ca[q], cb[q], nv);  // (on the way to LDS: the fetch stays in flight)
       *reinterpret_cast<u32x4*>(lb + ((u32)q * 16u + r16) * PWG_RS + c16 * 16u) = vb[q];
     }
     __syncthreads();
@@ -628,8 +707,10 @@ static bool pw_wgrad_plan(int B, int Cout, int Cin, int HW, PwgParams* p, int* m
 int reduce_rows_fixed_order(const float* src, float* mid, float* dst, unsigned n, unsigned rows, hipStream_t st);
 
 // dW = sum_b dy[b] x[b]^T with the images of x `xs` elements apart; arguments checked by the caller, except the workspace size
+// AF: x is read as op(x) with coef [Cin][4]
+template <bool AF = false>
 static int pw_wgrad_run(const void* dy, const void* x, size_t xs, float* dw, void* ws, size_t ws_bytes, int B, int Cout, int Cin, int HW,
-                        int dtype, hipStream_t stream, const char* what) {
+                        int dtype, hipStream_t stream, const char* what, const float* coef = nullptr) {
   PwgParams p;
   int mfw, nfw;
   const bool tiled = pw_wgrad_plan(B, Cout, Cin, HW, &p, &mfw, &nfw);
@@ -640,6 +721,7 @@ static int pw_wgrad_run(const void* dy, const void* x, size_t xs, float* dw, voi
   p.dy = (const u16*)dy;
   p.x = (const u16*)x;
   p.xs = xs;
+  p.coef = coef;
   p.ws = (float*)ws;
   p.B = B;
   p.Cout = Cout;
@@ -650,14 +732,14 @@ static int pw_wgrad_run(const void* dy, const void* x, size_t xs, float* dw, voi
   hipStream_t st = stream;
   if (tiled) {
     if (dtype == SSDK_BF16) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_tiled_kernel<SSDK_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PWG_LDS);
-      hipLaunchKernelGGL((pw_wgrad_tiled_kernel<SSDK_BF16>), grid, dim3(PWT_THREADS), PWG_LDS, st, p);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_tiled_kernel<SSDK_BF16, AF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PWG_LDS);
+      hipLaunchKernelGGL((pw_wgrad_tiled_kernel<SSDK_BF16, AF>), grid, dim3(PWT_THREADS), PWG_LDS, st, p);
     } else {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_tiled_kernel<SSDK_F16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PWG_LDS);
-      hipLaunchKernelGGL((pw_wgrad_tiled_kernel<SSDK_F16>), grid, dim3(PWT_THREADS), PWG_LDS, st, p);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_tiled_kernel<SSDK_F16, AF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PWG_LDS);
+      hipLaunchKernelGGL((pw_wgrad_tiled_kernel<SSDK_F16, AF>), grid, dim3(PWT_THREADS), PWG_LDS, st, p);
     }
   } else {
-#define SSDK_PWG(DT, MF_, NF_) hipLaunchKernelGGL((pw_wgrad_kernel<DT, MF_, NF_>), grid, dim3(PWT_THREADS), 0, st, p)
+#define SSDK_PWG(DT, MF_, NF_) hipLaunchKernelGGL((pw_wgrad_kernel<DT, MF_, NF_, AF>), grid, dim3(PWT_THREADS), 0, st, p)
 #define SSDK_PWGD(DT)                                  \
   do {                                                 \
     if (mfw == 3 && nfw == 2) SSDK_PWG(DT, 3, 2);      \

@@ -76,6 +76,19 @@ class Solver(object):
             # so the new DepthwiseConv2d / FastBatchNorm2d pairs get their statistics hand-off.  SSDK_SHUFFLE_TRAIN=0: chunk / cat /
             # channel_shuffle and nn.Conv2d.  Other backbones are not touched.
             shuffletrain.use_native_shuffle(self.model)
+        from ssds.modeling.layers import densetrain
+        from ssds.modeling.nets.densenet import DenseNet
+
+        if isinstance(getattr(self.model, "backbone", None), DenseNet) and densetrain.enabled():
+            # DenseNet backbones: a dense block trains on one feature buffer and one gradient buffer, norm1 + relu1
+            # applied by the first 1x1 on load (csrc/ssdk_densetrain.hip); swapped at block level, the layers keep their classes.
+            # SSDK_DENSE_TRAIN=0: _DenseBlock.forward, i.e. torch.cat and a full BatchNorm per layer.  The block's statistics are
+            # local sums, so with --sync-bn the blocks stay on the module path.  Other backbones are not touched.
+            if sync_bn:
+                if local_rank == 0:
+                    print("SSDK_DENSE_TRAIN: --sync-bn keeps the dense blocks on the module path (the block's statistics are local)")
+            else:
+                densetrain.use_native_dense_block(self.model)
         if os.environ.get("SSDK_PW_GEMM", "1") != "0":
             from ssds.modeling.layers.pointwise import use_pointwise_gemm
 

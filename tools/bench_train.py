@@ -156,12 +156,15 @@ if rank == 0:
     from ssds.modeling.layers import shuffletrain as _ST
 
     _shuffle = _ST.STATS["join_forward"] > 0  # SSDK_SHUFFLE_TRAIN: the units of a ShuffleNetV2 backbone ran their slice 1x1 / join natively
+    from ssds.modeling.layers import densetrain as _DT
+
+    _dense = _DT.STATS["native_forward"] > 0  # SSDK_DENSE_TRAIN: the dense blocks of a DenseNet backbone ran on one buffer
     _name = "SSD-MobileNetV2" if args.cfg == "ssd_mobilenetv2_512.yml" else "%s-%s" % (cfg.MODEL.SSDS, cfg.MODEL.NETS)
     print(json.dumps({"metric": "images/sec (DDP training step) %s@%d" % (_name, cfg.MODEL.IMAGE_SIZE[0]), "value": round(world * args.batch * args.steps / el, 1),
                       "n_gpus": world, "ms_per_step": round(el / args.steps * 1e3, 2), "batch_per_gpu": args.batch,
                       "cls_loss": float(c), "loc_loss": float(l), "dtype": "bf16 autocast", "hipgraph": bool(args.graph), "sync_bn": bool(args.sync_bn),
                       "optimizer": args.optimizer, "cfg": args.cfg, "gconv_train": os.environ.get("SSDK_GCONV_TRAIN", "1") != "0",
-                      "dense3_train": _dense3, "neck_train": _neck, "stem7_train": _stem7, "mbconv_train": _mbconv, "cat_train": _cat, "convt_train": _convt, "shuffle_train": _shuffle,
+                      "dense3_train": _dense3, "neck_train": _neck, "stem7_train": _stem7, "mbconv_train": _mbconv, "cat_train": _cat, "convt_train": _convt, "shuffle_train": _shuffle, "dense_train": _dense,
                       "peak_allocated_MiB": None if args.cpu else round(torch.cuda.max_memory_allocated() / 2 ** 20, 1),
                       "data": "synthetic" if not args.cpu else "stub (CPU / gloo run of the rank logic)"}))
 if world > 1:
