@@ -131,19 +131,27 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const BnParams p) {
         }
       }
     } else {
-      for (int i = threadIdx.x; i < p.HW; i += 256) {
-        const float xs = bn_ld1<DT>(p.x, base + i);
-        const float d = xs - k;
-        if (MODE == 0) {
-          a += d;
-          b += d * d;
-        } else {
-          float g = bn_ld1<DT>(p.dy, base + i);
-          // the mask is evaluated on x itself like the vector branch, the flat kernels and the forward clamp
-          // ((x - k) + k is not always x in floating point)
-          if (masked && !bn_act_open<DT>(xs * fa + fb, p.act)) g = 0.f;
-          a += g;
-          b += g * d * istd;
+      // element by element.  A plane of whole vectors that is only MISALIGNED keeps the vector branch's order of additions
+      // (thread t: elements t*VN .. t*VN + VN-1, then 256*VN further on), so a tensor's statistics do not depend on where
+      // its storage starts (tests/test_gpu_bntrain.py: a view 4 bytes into an allocation against the aligned call, fp32
+      // 16 x 24 planes -- the bits differed before).
+      const int vn = (p.HW % VN) == 0 ? VN : 1;
+      for (int i0 = threadIdx.x * vn; i0 < p.HW; i0 += 256 * vn) {
+        for (int e = 0; e < vn; ++e) {
+          const int i = i0 + e;  // < HW: i0 and HW are multiples of vn
+          const float xs = bn_ld1<DT>(p.x, base + i);
+          const float d = xs - k;
+          if (MODE == 0) {
+            a += d;
+            b += d * d;
+          } else {
+            float g = bn_ld1<DT>(p.dy, base + i);
+            // the mask is evaluated on x itself like the vector branch, the flat kernels and the forward clamp
+            // ((x - k) + k is not always x in floating point)
+            if (masked && !bn_act_open<DT>(xs * fa + fb, p.act)) g = 0.f;
+            a += g;
+            b += g * d * istd;
+          }
         }
       }
     }
@@ -583,8 +591,16 @@ static int bn_split(int N, int C) {
 // ticket words come first and their place depends on C alone, so launches with the same C never see them hold anything else.
 static size_t bn_round4(size_t n) { return (n + 3) & ~(size_t)3; }
 
+// What bn_launch launched, for ssdk_last_kernel(): [reduction][apply pass], joined by '+' (tests/test_gpu_bntrain.py asserts the
+// dispatch below through these names).
+static const char* const kBnLaunched[4][3] = {
+    {"", "bn_apply_kernel", "bn_apply_flat_kernel"},
+    {"bn_reduce_kernel", "bn_reduce_kernel+bn_apply_kernel", "bn_reduce_kernel+bn_apply_flat_kernel"},
+    {"bn_reduce_flat_kernel", "bn_reduce_flat_kernel+bn_apply_kernel", "bn_reduce_flat_kernel+bn_apply_flat_kernel"},
+    {"bn_fwd_finalize_kernel", "bn_fwd_finalize_kernel+bn_apply_kernel", "bn_fwd_finalize_kernel+bn_apply_flat_kernel"}};
+
 template <int MODE>
-static void bn_launch(const BnParams& p, hipStream_t st) {
+static const char* bn_launch(const BnParams& p, hipStream_t st) {
   // 0: the per-plane kernels, 1: the flat kernels, 2 (default): the flat reduction always, the flat apply pass only where
   // the per-plane one cannot use vectors (plane size not a multiple of the vector width, or a misaligned tensor: there it
   // works element by element).  Per launch on the 512 px step, bf16 (profiles/r02_train_kernel_split_v2.txt against a trace
@@ -622,6 +638,9 @@ static void bn_launch(const BnParams& p, hipStream_t st) {
   else if (p.dtype == SSDK_BF16) SSDK_BN(SSDK_BF16);
   else SSDK_BN(SSDK_F16);
 #undef SSDK_BN
+  const int reduced = (MODE == 0 && p.sums) ? 3 : p.apply_only ? 0 : flat_r ? 2 : 1;
+  const int applied = p.no_apply ? 0 : (flat && fgrid < (1l << 31)) ? 2 : 1;
+  return kBnLaunched[reduced][applied];
 }
 
 }  // namespace ssdk
@@ -686,8 +705,8 @@ extern "C" int ssdk_bn_act_train_fwd(const void* x, const float* weight, const f
   p.momentum = momentum;
   p.eps = eps;
   p.act = act;
-  bn_launch<0>(p, (hipStream_t)stream);
-  return check_launch("bn_train_fwd");
+  const char* launched = bn_launch<0>(p, (hipStream_t)stream);
+  return check_launch(launched);
 }
 
 extern "C" int ssdk_bn_act_train_fwd_sums(const void* x, const float* sums, const float* weight, const float* bias,
@@ -719,8 +738,8 @@ extern "C" int ssdk_bn_act_train_fwd_sums(const void* x, const float* sums, cons
   p.momentum = momentum;
   p.eps = eps;
   p.act = act;
-  bn_launch<0>(p, (hipStream_t)stream);
-  return check_launch("bn_train_fwd_sums");
+  const char* launched = bn_launch<0>(p, (hipStream_t)stream);
+  return check_launch(launched);
 }
 
 // The forward pass WITHOUT its apply pass: batch statistics (from `sums` when the producer provided them, else by the reduction
@@ -752,8 +771,8 @@ extern "C" int ssdk_bn_act_train_stats(const void* x, const float* sums, const f
   p.save_invstd = save_invstd;
   p.momentum = momentum;
   p.eps = eps;
-  bn_launch<0>(p, (hipStream_t)stream);
-  return check_launch("bn_train_stats");
+  const char* launched = bn_launch<0>(p, (hipStream_t)stream);
+  return check_launch(launched);
 }
 
 extern "C" int ssdk_bn_train_fwd(const void* x, const float* weight, const float* bias, float* running_mean,
@@ -790,8 +809,8 @@ extern "C" int ssdk_bn_act_train_bwd(const void* x, const void* dy, const float*
   p.save_invstd = const_cast<float*>(save_invstd);
   p.dweight = dweight;
   p.dbias = dbias;
-  bn_launch<1>(p, (hipStream_t)stream);
-  return check_launch("bn_train_bwd");
+  const char* launched = bn_launch<1>(p, (hipStream_t)stream);
+  return check_launch(launched);
 }
 
 extern "C" int ssdk_bn_train_bwd(const void* x, const void* dy, const float* weight, const float* save_mean,
@@ -837,8 +856,8 @@ extern "C" int ssdk_bn_sync_local_stats(const void* x, const float* sums, float*
   p.sums = sums;  // the producer's raw sums: the launch only packs them (pivot 0)
   p.no_apply = 1;
   p.send = send;
-  bn_launch<0>(p, (hipStream_t)stream);
-  return check_launch("bn_sync_local_stats");
+  const char* launched = bn_launch<0>(p, (hipStream_t)stream);
+  return check_launch(launched);
 }
 
 extern "C" int ssdk_bn_sync_fwd_finalize(const float* gathered, int W, const float* weight, const float* bias, float* running_mean,
@@ -867,7 +886,7 @@ extern "C" int ssdk_bn_sync_fwd_finalize(const float* gathered, int W, const flo
   p.momentum = momentum;
   p.eps = eps;
   hipLaunchKernelGGL(bn_sync_fwd_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p);
-  return check_launch("bn_sync_fwd_finalize");
+  return check_launch("bn_sync_fwd_finalize_kernel");
 }
 
 // the forward apply pass alone: y = act(a x + b) with coef [C][4] = (a, b, ., .) as ssdk_bn_act_train_stats /
@@ -894,8 +913,8 @@ extern "C" int ssdk_bn_act_apply(const void* x, const float* coef, void* y, int 
   p.coef = const_cast<float*>(coef);
   p.act = act;
   p.apply_only = 1;
-  bn_launch<0>(p, (hipStream_t)stream);
-  return check_launch("bn_act_apply");
+  const char* launched = bn_launch<0>(p, (hipStream_t)stream);
+  return check_launch(launched);
 }
 
 extern "C" int ssdk_bn_sync_bwd_local(const void* x, const void* dy, const float* weight, const float* bias, const float* save_mean,
@@ -934,8 +953,8 @@ extern "C" int ssdk_bn_sync_bwd_local(const void* x, const void* dy, const float
   p.dbias = dbias;
   p.send = send;
   p.no_apply = 1;
-  bn_launch<1>(p, (hipStream_t)stream);
-  return check_launch("bn_sync_bwd_local");
+  const char* launched = bn_launch<1>(p, (hipStream_t)stream);
+  return check_launch(launched);
 }
 
 extern "C" int ssdk_bn_sync_bwd_apply(const void* x, const void* dy, const float* gathered, int W, const float* fwd_gathered,
@@ -968,6 +987,6 @@ extern "C" int ssdk_bn_sync_bwd_apply(const void* x, const void* dy, const float
   p.fwd_gathered = fwd_gathered;
   p.W = W;
   p.apply_only = 1;
-  bn_launch<1>(p, (hipStream_t)stream);
-  return check_launch("bn_sync_bwd_apply");
+  const char* launched = bn_launch<1>(p, (hipStream_t)stream);
+  return check_launch(launched);
 }

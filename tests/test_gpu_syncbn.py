@@ -1,7 +1,7 @@
 """Synchronised BatchNorm on the HIP kernels (csrc/ssdk_bntrain.hip, "synchronised BatchNorm"; batchnorm.use_fast_sync_batchnorm).
 
 1. emulated ranks in one process: unequal shards of one batch (one of them empty) through the split entry points, against fp64
-   torch on the whole batch;
+   torch on the whole batch (one max-norm per tensor; per channel against derived bars: tests/test_gpu_bntrain.py);
 2. one rank IS the local path: the split entry points at W = 1 give the bits of ssdk_bn_act_train_fwd / _stats / _bwd;
 3. two real ranks (gloo, both on cuda:0): against torch.nn.SyncBatchNorm and fp64, identical statistics on both ranks, and two
    DDP steps of the training Solver with --sync-bn end with identical replicas;
@@ -15,6 +15,8 @@ import sys
 
 import pytest
 import torch
+
+from bnjudge import split_path as _split_path  # (moved there: tests/test_gpu_bntrain.py judges the same path per channel)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = {"float32": 2e-4, "bfloat16": 2e-2, "float16": 4e-3}
@@ -83,51 +85,6 @@ def _ws(n, c):
 
 def _ptr(t):
     return t.data_ptr() if t.numel() else None
-
-
-def _split_path(shards, dys, weight, bias, rm, rv, momentum, eps, act, sums=None):
-    """Every shard as one rank: local records -> stacked (the all-gather) -> merge -> apply; backward the same way."""
-    from ssds import _native as N
-
-    L, st = N.lib, N.stream_ptr(torch.device("cuda"))
-    c = int(shards[0].shape[1])
-    hw = int(shards[0].shape[2] * shards[0].shape[3])
-    sends = []
-    for i, x in enumerate(shards):
-        send = torch.empty(3 * c + 1, device="cuda")
-        ws, need = _ws(x.shape[0], c)
-        s = None if sums is None else sums[i].data_ptr()
-        N.check(L.ssdk_bn_sync_local_stats(_ptr(x), s, send.data_ptr(), ws.data_ptr(), need, x.shape[0], c, hw, N.dtype_code(x), st),
-                "local_stats")
-        sends.append(send)
-    gathered = torch.stack(sends)
-    mean, invstd = torch.empty(c, device="cuda"), torch.empty(c, device="cuda")
-    coef = torch.empty(c, 4, device="cuda")
-    N.check(L.ssdk_bn_sync_fwd_finalize(gathered.data_ptr(), len(shards), weight.data_ptr(), bias.data_ptr(), rm.data_ptr(),
-                                        rv.data_ptr(), mean.data_ptr(), invstd.data_ptr(), coef.data_ptr(), c, momentum, eps, st),
-            "fwd_finalize")
-    ys, bsends, dws, dbs = [], [], [], []
-    for x, dy in zip(shards, dys):
-        y = torch.empty_like(x)
-        N.check(L.ssdk_bn_act_apply(_ptr(x), coef.data_ptr(), _ptr(y), x.shape[0], c, hw, act, N.dtype_code(x), st), "apply")
-        ys.append(y)
-        send, dw, db = torch.empty(2 * c, device="cuda"), torch.empty(c, device="cuda"), torch.empty(c, device="cuda")
-        ws, need = _ws(x.shape[0], c)
-        N.check(L.ssdk_bn_sync_bwd_local(_ptr(x), _ptr(dy), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                         send.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), need, x.shape[0], c, hw, act,
-                                         N.dtype_code(x), st), "bwd_local")
-        bsends.append(send)
-        dws.append(dw)
-        dbs.append(db)
-    bgathered = torch.stack(bsends)
-    dxs = []
-    for x, dy in zip(shards, dys):
-        dx = torch.empty_like(x)
-        N.check(L.ssdk_bn_sync_bwd_apply(_ptr(x), _ptr(dy), bgathered.data_ptr(), len(shards), gathered.data_ptr(), weight.data_ptr(),
-                                         bias.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(dx), x.shape[0], c, hw, act,
-                                         N.dtype_code(x), st), "bwd_apply")
-        dxs.append(dx)
-    return dict(y=ys, mean=mean, invstd=invstd, coef=coef, dx=dxs, dw=dws, db=dbs)
 
 
 @pytest.mark.gpu

@@ -345,7 +345,8 @@ def test_depthwise_autograd_kernels_match_torch(c, stride, h, w, n, dtype_name, 
                                      # many small planes per workgroup with vectors that straddle planes, 1 x 1 planes
                                      (2, 6, 150, 150), (1, 4, 100, 100), (70, 3, 10, 10), (5, 7, 19, 19), (9, 5, 1, 1)])
 def test_batchnorm_training_kernels_match_torch(n, c, h, w, dtype_name, tol):
-    """forward (output, running statistics) and backward (dx, dweight, dbias) vs nn.BatchNorm2d in fp32."""
+    """forward (output, running statistics) and backward (dx, dweight, dbias) vs nn.BatchNorm2d in fp32.
+    One max-norm per tensor; per channel and per element against fp64 with derived bars: tests/test_gpu_bntrain.py."""
     import torch
     import torch.nn as nn
     from ssds.modeling.layers.batchnorm import FastBatchNorm2d
