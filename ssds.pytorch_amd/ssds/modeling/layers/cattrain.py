@@ -11,8 +11,6 @@ every window from the saved input (first maximum in row-major window order under
 only ``x``.
 
 ``use_native_cat(model)`` enables the path per model; a model it was never called on runs the earlier expressions."""
-import os
-
 import torch
 
 from ssds import _native as N
@@ -164,13 +162,9 @@ def try_spp(x):
         return _Spp.apply(srcs[0])
 
 
-DEFAULT = "1"  # docs/SWITCHES.md, DESIGN.md 4.5h
-
-
-def enabled():
-    """SSDK_CAT_TRAIN (docs/SWITCHES.md): 1 routes the channel concatenations and the SPP block of the YOLOV3 / YOLOV4 training step
-    to csrc/ssdk_cattrain.hip, 0 leaves them on torch's cat / interpolate / max_pool2d."""
-    return os.environ.get("SSDK_CAT_TRAIN", DEFAULT) != "0"
+# what an unset SSDK_CAT_TRAIN means (train_routing.PASSES; docs/SWITCHES.md): 1 routes the channel concatenations and
+# the SPP block of the YOLOV3 / YOLOV4 training step to csrc/ssdk_cattrain.hip, 0 leaves them on torch's cat / interpolate / max_pool2d
+DEFAULT = "1"
 
 
 def spp_supported(m):

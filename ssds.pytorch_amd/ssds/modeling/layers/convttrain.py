@@ -20,8 +20,6 @@ non-contiguous tensors and every other layer shape take ``nn.ConvTranspose2d.for
 
 The images are packed again by every call (one small launch): the native optimizers update parameters through raw pointers, so no
 tensor version counter says when a cached image is stale."""
-import os
-
 import torch
 import torch.nn as nn
 
@@ -238,13 +236,7 @@ class ShelfConvT(nn.ConvTranspose2d):
 # the module path on shelf_resnet18_513 -- 50.34 against 47.36 ms per step with the switch off, 48.00 ms on the parent commit, spreads
 # under 0.1 ms -- so the routing is off unless SSDK_CONVT_TRAIN=1.  The weight-gradient pass is what loses (about 780 us against 130 us
 # per layer): its 32-pixel steps are half empty on the 17- and 33-wide maps
-DEFAULT = "0"
-
-
-def enabled():
-    """SSDK_CONVT_TRAIN (docs/SWITCHES.md): 1 routes the transposed convolutions of the SSDShelf training step (+ bias + skip
-    map) to csrc/ssdk_convttrain.hip, 0 leaves them on nn.ConvTranspose2d and the eager add."""
-    return os.environ.get("SSDK_CONVT_TRAIN", DEFAULT) != "0"
+DEFAULT = "0"  # (train_routing.PASSES reads it; 0 leaves the layers on nn.ConvTranspose2d and the eager add)
 
 
 def use_native_convt(model):

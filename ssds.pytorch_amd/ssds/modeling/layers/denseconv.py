@@ -16,8 +16,6 @@ tensors, non-contiguous tensors and every other layer shape take ``nn.Conv2d.for
 
 The images are packed again by every call (one small launch): the native optimizers update parameters through raw pointers,
 so no tensor version counter says when a cached image is stale."""
-import os
-
 import torch
 import torch.nn as nn
 
@@ -167,20 +165,16 @@ class DenseConv3x3(nn.Conv2d):
             return _DenseConv3x3.apply(x, w, self.bias, self.stride[0])
 
 
-DEFAULT = "1"  # provisional (docs/SWITCHES.md): to be re-decided from the per-layer probe and the step A/B
+# what an unset SSDK_DENSE3_TRAIN means on SSDFPN / SSDBiFPN models (train_routing.PASSES picks between this and YOLO_DEFAULT by the
+# model): 1 routes the dense 3x3 layers of the training step to csrc/ssdk_conv3train.hip, 0 leaves them on nn.Conv2d (extras: the im2col
+# path).  Provisional (docs/SWITCHES.md): to be re-decided from the per-layer probe and the step A/B
+DEFAULT = "1"
 
 
 # YOLOV3 / YOLOV4 models (docs/SWITCHES.md): every 3x3 of both shipped configs fits the kernels, and the step A/B at
 # batch 32 (profiles/r15_train_step_yolo_ab.jsonl) has them SLOWER than nn.Conv2d on these ResNet-18 models -- 14.44 vs 11.43 ms
 # (yolov3_resnet18_320), 28.45 vs 22.02 ms (yolov4_resnet18_512) -- so on YOLO models the routing is off unless SSDK_DENSE3_TRAIN=1
-YOLO_DEFAULT = "0"
-
-
-def enabled(default=None):
-    """SSDK_DENSE3_TRAIN (docs/SWITCHES.md): 1 routes the dense 3x3 layers of the SSDFPN / SSDBiFPN (and YOLOV3 / YOLOV4) training
-    step to csrc/ssdk_conv3train.hip, 0 leaves them on nn.Conv2d (extras: the im2col path).  ``default``: what an unset variable
-    means (DEFAULT; train_ddp.Solver passes YOLO_DEFAULT for the YOLO models)."""
-    return os.environ.get("SSDK_DENSE3_TRAIN", DEFAULT if default is None else default) != "0"
+YOLO_DEFAULT = "0"  # (SSDShelf models too: never timed there, slower on the other ResNet-18 models)
 
 
 def use_native_dense3x3(model):

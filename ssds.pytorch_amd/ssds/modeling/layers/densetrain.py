@@ -29,7 +29,6 @@ The swap is at block level (``use_native_dense_block`` sets ``block.__class__``)
 ``state_dict`` keys.  Eval mode, CPU tensors, fp32 without autocast, ``drop_rate > 0`` and synchronised BatchNorm layers run
 ``_DenseBlock.forward`` (counted in STATS["fallback"], reasons in FALLBACK_REASONS).  DESIGN.md 4.5o."""
 import collections
-import os
 
 import torch
 import torch.nn as nn
@@ -348,10 +347,6 @@ def use_native_dense_block(model):
     return n
 
 
-DEFAULT = "0"  # docs/SWITCHES.md, DESIGN.md 4.5o
-
-
-def enabled():
-    """SSDK_DENSE_TRAIN (docs/SWITCHES.md): 1 routes the dense blocks of a DenseNet backbone's training step to
-    csrc/ssdk_densetrain.hip, 0 leaves them on ``_DenseBlock.forward`` (torch.cat and a full BatchNorm per layer)."""
-    return os.environ.get("SSDK_DENSE_TRAIN", DEFAULT) != "0"
+# what an unset SSDK_DENSE_TRAIN means (train_routing.PASSES; docs/SWITCHES.md): 1 routes the dense blocks of a DenseNet
+# backbone's training step to csrc/ssdk_densetrain.hip, 0 leaves them on ``_DenseBlock.forward`` (torch.cat and a full BatchNorm per layer)
+DEFAULT = "0"

@@ -12,8 +12,6 @@ forward / backward run on the ssdk kernels:
 
 pad 1, stride 1 | 2, Cin == Cout == groups * gw with gw = 4 (an even number of groups) or a multiple of 8 up to 256.  CPU
 tensors, fp32 tensors, non-contiguous tensors and every other layer shape take ``nn.Conv2d.forward``."""
-import os
-
 import torch
 import torch.nn as nn
 
@@ -160,11 +158,6 @@ class GroupedConv3x3(nn.Conv2d):
             return super(GroupedConv3x3, self).forward(x)
         with torch.autocast("cuda", enabled=False):
             return _GroupedConv3x3.apply(x, w, self.bias, self.stride[0], self.groups)
-
-
-def enabled():
-    """SSDK_GCONV_TRAIN (default 1; docs/SWITCHES.md): 0 leaves the grouped 3x3 layers of the training step on nn.Conv2d."""
-    return os.environ.get("SSDK_GCONV_TRAIN", "1") != "0"
 
 
 def use_native_gconv(model):

@@ -3,8 +3,6 @@
 function of that BatchNorm's output ``u`` -- ``z = silu(u) * g``, ``g = sigmoid(W2 silu(W1 mean_hw(silu(u)) + b1) + b2)`` -- whose
 ``silu(u)`` is never stored.  The swap is at BLOCK level (``use_native_mbconv`` sets ``blk.__class__``): the convolution modules keep
 their classes, parameters and ``state_dict`` keys.  DESIGN.md 4.6b."""
-import os
-
 import torch
 
 from ssds import _native as N
@@ -270,10 +268,6 @@ def use_native_mbconv(model):
     return n
 
 
-DEFAULT = "1"  # docs/SWITCHES.md, DESIGN.md 4.6b
-
-
-def enabled():
-    """SSDK_MBCONV_TRAIN: "0" leaves the MBConv blocks on ``MBConvBlock.forward`` (the library's 5x5 depthwise kernels and the eager
-    SiLU / pool / 1x1 / multiply passes)."""
-    return os.environ.get("SSDK_MBCONV_TRAIN", DEFAULT) != "0"
+# what an unset SSDK_MBCONV_TRAIN means (train_routing.PASSES; docs/SWITCHES.md): "0" leaves the MBConv blocks on
+# ``MBConvBlock.forward`` (the library's 5x5 depthwise kernels and the eager SiLU / pool / 1x1 / multiply passes)
+DEFAULT = "1"

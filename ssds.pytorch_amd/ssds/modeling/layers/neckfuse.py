@@ -12,8 +12,6 @@ column of the fast-normalised fp32 [K, L] tensor BiFPNModule.forward computes: n
 recomputes the arg-max from the saved input (first maximum in row-major window order, torch's rule).
 
 ``use_native_neck(model)`` enables the path per model; a model it was never called on runs the earlier expressions."""
-import os
-
 import torch
 import torch.nn as nn
 
@@ -223,13 +221,10 @@ class TrainMaxPool3x3s2(nn.MaxPool2d):
         return _MaxPool3x3s2.apply(x)
 
 
-DEFAULT = "1"  # docs/SWITCHES.md, DESIGN.md 4.5d: every probed case and both step A/Bs favour the kernels
-
-
-def enabled():
-    """SSDK_NECK_TRAIN (docs/SWITCHES.md): 1 routes the fusions, the top-down adds and the stem max-pool of the SSDFPN / SSDBiFPN
-    training step to csrc/ssdk_necktrain.hip, 0 leaves them on the eager expressions."""
-    return os.environ.get("SSDK_NECK_TRAIN", DEFAULT) != "0"
+# what an unset SSDK_NECK_TRAIN means (train_routing.PASSES; docs/SWITCHES.md): every probed case and both step A/Bs
+# favour the kernels.  1 routes the fusions, the top-down adds and the stem max-pool of the SSDFPN / SSDBiFPN training step to
+# csrc/ssdk_necktrain.hip, 0 leaves them on the eager expressions
+DEFAULT = "1"
 
 
 def use_native_neck(model):

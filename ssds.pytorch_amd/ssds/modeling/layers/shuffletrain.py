@@ -339,13 +339,9 @@ def try_unit(unit, x):
         return _Join.apply(xk.detach(), rk[0], True, share)
 
 
-DEFAULT = "1"  # docs/SWITCHES.md, DESIGN.md 4.5n
-
-
-def enabled():
-    """SSDK_SHUFFLE_TRAIN (docs/SWITCHES.md): 1 routes the ShuffleNetV2 units of the training step to csrc/ssdk_shuffletrain.hip and
-    the project's depthwise kernels, 0 leaves them on chunk / cat / channel_shuffle and nn.Conv2d."""
-    return os.environ.get("SSDK_SHUFFLE_TRAIN", DEFAULT) != "0"
+# what an unset SSDK_SHUFFLE_TRAIN means (train_routing.PASSES; docs/SWITCHES.md): 1 routes the ShuffleNetV2 units of the
+# training step to csrc/ssdk_shuffletrain.hip and the project's depthwise kernels, 0 leaves them on chunk / cat / channel_shuffle and nn.Conv2d
+DEFAULT = "1"
 
 
 def _dense_1x1(m):

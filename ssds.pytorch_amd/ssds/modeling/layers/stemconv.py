@@ -2,8 +2,6 @@
 (nets/resnet.py conv1) on csrc/ssdk_stem7train.hip -- forward and weight gradient on the 16-bit NCHW tensors autograd hands over,
 with the fp32 master weight rounded inside the kernel (no per-step cast of the parameter, no layout transposes).  The image has
 no gradient; if somebody asks for one it comes from the framework's convolution backward.  DESIGN.md 4.5e."""
-import os
-
 import torch
 import torch.nn as nn
 
@@ -109,9 +107,6 @@ def use_native_stem7(model):
     return n
 
 
-DEFAULT = "0"  # docs/SWITCHES.md, DESIGN.md 4.5e: nothing measured yet, so the library routing stays the default
-
-
-def enabled():
-    """SSDK_STEM7_TRAIN: "0" leaves the 7x7 stem on nn.Conv2d (the library convolution behind autocast's weight cast)."""
-    return os.environ.get("SSDK_STEM7_TRAIN", DEFAULT) != "0"
+# what an unset SSDK_STEM7_TRAIN means (train_routing.PASSES; docs/SWITCHES.md): nothing measured yet, so the library
+# routing stays the default.  "0" leaves the 7x7 stem on nn.Conv2d (the library convolution behind autocast's weight cast)
+DEFAULT = "0"

@@ -23,7 +23,7 @@ from torch.nn.parallel import DistributedDataParallel as DDP
 
 from ssds.core import checkpoint, config, criterion, optimizer
 from ssds.dataset.synthetic import SyntheticDetectionLoader
-from ssds.modeling import model_builder
+from ssds.modeling import model_builder, train_routing
 from ssds.pipeline.pipeline_anchor_ddp import ModelWithLossBasic, train_anchor_based_epoch
 
 
@@ -50,146 +50,7 @@ class Solver(object):
             print("===> Building model")
         self.model = model_builder.create_model(cfg.MODEL)
         self.load_model()
-        fast_bn = os.environ.get("SSDK_FAST_BN", "1") != "0"
-        if sync_bn and not fast_bn:
-            self.model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(self.model)
-        elif fast_bn:
-            from ssds.modeling.layers.batchnorm import use_fast_batchnorm, use_fast_sync_batchnorm
-
-            if sync_bn:
-                use_fast_sync_batchnorm(self.model)  # statistics over all ranks, on the same kernels and fusions
-            else:
-                use_fast_batchnorm(self.model)  # training BN on the ssdk kernels (local statistics, like the default)
-            if os.environ.get("SSDK_FUSE_BN_ACT", "1") != "0":
-                from ssds.modeling.layers.batchnorm import fuse_bn_activations
-
-                fuse_bn_activations(self.model)  # Conv-BN-ReLU6: the clamp and its gradient mask ride on the BN passes
-                from ssds.modeling.layers.batchnorm import fuse_bn_into_depthwise
-
-                fuse_bn_into_depthwise(self.model)  # expand BN (+ ReLU6) applied by the depthwise kernels on load: no apply pass
-        from ssds.modeling.layers import shuffletrain
-        from ssds.modeling.nets.shufflenet import ShuffleNetV2
-
-        if shuffletrain.enabled() and isinstance(getattr(self.model, "backbone", None), ShuffleNetV2):
-            # ShuffleNetV2 backbones: the units' slice 1x1 and join on csrc/ssdk_shuffletrain.hip, their depthwise 3x3
-            # on the project's depthwise kernels, 1x1 layers of any width.  After the BatchNorm swap and before the two calls below,
-            # so the new DepthwiseConv2d / FastBatchNorm2d pairs get their statistics hand-off.  SSDK_SHUFFLE_TRAIN=0: chunk / cat /
-            # channel_shuffle and nn.Conv2d.  Other backbones are not touched.
-            shuffletrain.use_native_shuffle(self.model)
-        from ssds.modeling.layers import densetrain
-        from ssds.modeling.nets.densenet import DenseNet
-
-        if isinstance(getattr(self.model, "backbone", None), DenseNet) and densetrain.enabled():
-            # DenseNet backbones: a dense block trains on one feature buffer and one gradient buffer, norm1 + relu1
-            # applied by the first 1x1 on load (csrc/ssdk_densetrain.hip); swapped at block level, the layers keep their classes.
-            # SSDK_DENSE_TRAIN=0: _DenseBlock.forward, i.e. torch.cat and a full BatchNorm per layer.  The block's statistics are
-            # local sums, so with --sync-bn the blocks stay on the module path.  Other backbones are not touched.
-            if sync_bn:
-                if local_rank == 0:
-                    print("SSDK_DENSE_TRAIN: --sync-bn keeps the dense blocks on the module path (the block's statistics are local)")
-            else:
-                densetrain.use_native_dense_block(self.model)
-        if os.environ.get("SSDK_PW_GEMM", "1") != "0":
-            from ssds.modeling.layers.pointwise import use_pointwise_gemm
-
-            use_pointwise_gemm(self.model)  # 1x1 convolutions on the NCHW tensors (16 bit: csrc/ssdk_pwtrain.hip; fp32: library GEMMs)
-            if fast_bn:
-                from ssds.modeling.layers.pointwise import fuse_conv_bn_statistics
-
-                fuse_conv_bn_statistics(self.model)  # the 1x1 kernels hand their BatchNorm the (local) batch statistics
-        from ssds.modeling.layers import groupedconv
-
-        if groupedconv.enabled():
-            # grouped 3x3 of the RegNetX / ResNeXt bottlenecks: forward, input gradient, weight gradient on csrc/ssdk_gconvtrain.hip
-            # (SSDK_GCONV_TRAIN=0: nn.Conv2d, i.e. MIOpen's grouped convolution behind autocast's weight cast)
-            groupedconv.use_native_gconv(self.model)
-        from ssds.modeling.layers.pointwise import use_native_stem
-
-        use_native_stem(self.model)  # the image-side 3x3 / stride-2 convolution: forward + weight gradient on csrc/ssdk_stemtrain.hip (A/B tools/run/r06_s42.sh: 17.0 vs 17.5 ms per step)
-        from ssds.modeling.layers import stemconv
-
-        if stemconv.enabled():
-            # the 7x7 / stride-2 stem of the ResNet / ResNeXt backbones (any detector on them): forward + weight gradient on
-            # csrc/ssdk_stem7train.hip.  SSDK_STEM7_TRAIN=0: nn.Conv2d, i.e. the library convolution behind autocast's weight cast
-            stemconv.use_native_stem7(self.model)
-        from ssds.modeling.layers import mbconvtrain
-
-        if mbconvtrain.enabled():
-            # the EfficientNet MBConv blocks: 5x5 depthwise forward / gradients and SiLU + squeeze-excite on csrc/ssdk_mbconvtrain.hip,
-            # swapped at block level (the convolution modules keep their classes).  SSDK_MBCONV_TRAIN=0: MBConvBlock.forward, i.e.
-            # the library's depthwise kernels and the eager SiLU / pool / 1x1 / multiply passes.  Any model: others have no such block
-            mbconvtrain.use_native_mbconv(self.model)
-        from ssds.modeling.layers.headconv import use_head_pairs
-
-        use_head_pairs(self.model)  # SSD heads: forward of each level's loc | conf pair on the inference kernels (SSDK_HEAD_PAIR=0: MIOpen)
-        from ssds.modeling.layers import denseconv
-        from ssds.modeling.ssds.bifpn import SSDBiFPN
-        from ssds.modeling.ssds.fpn import SSDFPN
-        from ssds.modeling.ssds.yolo import YOLOV3, YOLOV4
-
-        yolo = isinstance(self.model, (YOLOV3, YOLOV4))
-        if isinstance(self.model, (SSDFPN, SSDBiFPN)) and denseconv.enabled():
-            # dense 3x3 of the FPN / BiFPN detectors (towers, smoothing, heads, ResNet bottlenecks, extras): forward, input gradient,
-            # weight gradient on csrc/ssdk_conv3train.hip.  Before the im2col swap below, which then skips the extras of these
-            # models (no longer plain nn.Conv2d).  SSDK_DENSE3_TRAIN=0: nn.Conv2d / the im2col extras.  SSD models are not touched.
-            denseconv.use_native_dense3x3(self.model)
-        from ssds.modeling.layers import neckfuse
-
-        if isinstance(self.model, (SSDFPN, SSDBiFPN)) and neckfuse.enabled():
-            # the BiFPN weighted fusions, the FPN top-down upsample-adds and the ResNet stem's max-pool: forward and backward on
-            # csrc/ssdk_necktrain.hip.  SSDK_NECK_TRAIN=0: the eager expressions / nn.MaxPool2d.  SSD models are not touched.
-            neckfuse.use_native_neck(self.model)
-        if yolo:
-            # YOLOv3 / YOLOv4, each part under its own switch.  SSDK_DENSE3_TRAIN: every 3x3 of both shipped configs
-            # (transforms, ConvBNReLUx2, heads, PAN stride-2 layers, ResNet BasicBlocks) fits csrc/ssdk_conv3train.hip -- before the
-            # im2col swap below, which then skips the extras; measured slower than nn.Conv2d on these models, so here an unset
-            # variable means 0 (denseconv.YOLO_DEFAULT).  SSDK_NECK_TRAIN: the ResNet stem max-pool on csrc/ssdk_necktrain.hip (all
-            # use_native_neck touches on these models).  SSDK_CAT_TRAIN: the concatenations and the SPP block on csrc/ssdk_cattrain.hip.
-            from ssds.modeling.layers import cattrain
-
-            if denseconv.enabled(denseconv.YOLO_DEFAULT):
-                denseconv.use_native_dense3x3(self.model)
-            if neckfuse.enabled():
-                neckfuse.use_native_neck(self.model)
-            if cattrain.enabled():
-                cattrain.use_native_cat(self.model)
-        from ssds.modeling.ssds.shelf import SSDShelf
-
-        if isinstance(self.model, SSDShelf):
-            # SSDShelf, each part under its own switch.  SSDK_CONVT_TRAIN: the decoders' transposed 3x3 / stride 2 +
-            # bias + skip add, forward and gradients on csrc/ssdk_convttrain.hip; the step measured slower with it (50.34 against
-            # 47.36 ms at batch 32), so an unset variable means 0 (convttrain.DEFAULT).  SSDK_DENSE3_TRAIN: the SharedBlock 3x3 (one weight
-            # on two maps), the encoder's stride-2 layers, the heads and the ResNet blocks fit csrc/ssdk_conv3train.hip -- before the
-            # im2col swap below; those kernels measured slower than nn.Conv2d on ResNet-18 models and were never timed on Shelf, so
-            # here an unset variable means 0, as on YOLO (denseconv.YOLO_DEFAULT).  SSDK_NECK_TRAIN: the ResNet stem max-pool on
-            # csrc/ssdk_necktrain.hip (all use_native_neck touches on this model).
-            from ssds.modeling.layers import convttrain
-
-            if convttrain.enabled():
-                convttrain.use_native_convt(self.model)
-            if denseconv.enabled(denseconv.YOLO_DEFAULT):
-                denseconv.use_native_dense3x3(self.model)
-            if neckfuse.enabled():
-                neckfuse.use_native_neck(self.model)
-        conv3 = os.environ.get("SSDK_CONV3_NATIVE", "2")
-        from ssds.modeling.layers import headconv
-
-        headconv.WGRAD_MIN_PIXELS = 64 if conv3 == "0" else 0
-        if conv3 == "2" and hasattr(self.model, "extras"):
-            # (default) NO library convolution in the step: the extras' 3x3 / stride-2 layers as im2col + ssdk_pw_* + col2im with the
-            # batch folded into the GEMM's pixel dimension (64 / 16 / 4 / 1 pixels per image: pointwise.FOLD_BELOW), and the weight
-            # gradients of the small head levels on ssdk_pw_wgrad the same way.  tools/run/r06_s53.sh: 16.7 vs 17.0 ms per step
-            # against the library (SSDK_CONV3_NATIVE=0); before the fold the same path was 0.6 ms SLOWER than the library
-            from ssds.modeling.layers.pointwise import use_native_conv3x3
-
-            use_native_conv3x3(self.model.extras)
-        if conv3 == "1":
-            # EVERY 3x3 layer (the heads too) as im2col + the 1x1 kernels.  Correct (tests/test_gpu_train.py) and slow: 23.2 vs
-            # 20.8 ms per step when it was measured (round 6, session 4: the streaming 1x1 kernels are the wrong shape for
-            # K = 864 ... 4608 at 480 output channels; the heads run on the inference kernels instead: headconv.py)
-            from ssds.modeling.layers.pointwise import use_native_conv3x3
-
-            use_native_conv3x3(self.model)
+        train_routing.route_for_training(self.model, sync_bn=sync_bn, local_rank=local_rank)  # the kernel families, in table order
         self.model.to(self.device)
         if render and local_rank == 0:
             print("Model architectures:\n{}\n".format(self.model))

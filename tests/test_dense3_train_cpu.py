@@ -2,10 +2,10 @@
 no GPU: the exported entry points and their argument checks, the layout of the two weight images, which layers
 ``use_native_dense3x3`` swaps, and the Solver's routing under SSDK_DENSE3_TRAIN."""
 import os
-import subprocess
-import sys
 
 import pytest
+
+from solverhelp import run_solver_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -148,8 +148,6 @@ def test_use_native_dense3x3_swaps_exactly_the_supported_layers():
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 from ssds.core import config
 from ssds.utils import train_ddp
 from ssds.modeling.layers import denseconv as D
@@ -171,14 +169,7 @@ print("RESULT", len(dense), native, anywhere, im2col_extras, im2col_other, plain
 
 
 def _solver(cfg_name, switch):
-    env = dict(os.environ)
-    env.pop("SSDK_DENSE3_TRAIN", None)
-    if switch is not None:
-        env["SSDK_DENSE3_TRAIN"] = switch
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"), cfg=os.path.join(ROOT, "experiments", "cfgs", cfg_name))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return [int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:]]
+    return run_solver_script(_SOLVER, cfg_name, env={"SSDK_DENSE3_TRAIN": switch})
 
 
 @pytest.mark.parametrize("cfg_name", ["fpn_resnet50_640.yml", "fpn_resnext50_640.yml", "bifpn_regnetx016_896.yml"])

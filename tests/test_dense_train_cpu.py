@@ -4,12 +4,11 @@ blocks ``use_native_dense_block`` switches, that a switched model computes bit f
 ``supported`` refuses, the Solver's routing, and the summation-depth twins against the library's workspace queries."""
 import copy
 import os
-import subprocess
-import sys
 
 import pytest
 
 import densejudge as DJ
+from solverhelp import run_solver_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ssdk_dense_train_place_workspace_bytes", "ssdk_dense_train_place", "ssdk_dense_train_pw_forward", "ssdk_dense_train_pw_wgrad",
@@ -191,8 +190,6 @@ def test_supported_refuses_by_name():
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 from ssds.core import config
 from ssds.utils import train_ddp
 from ssds.modeling.layers import densetrain as DT
@@ -205,14 +202,7 @@ print("RESULT", len(blocks), sum(type(m) is DT.TrainDenseBlock for m in blocks),
 
 
 def _solver(cfg_name, switch, sync=False):
-    env = dict(os.environ)
-    env.pop("SSDK_DENSE_TRAIN", None)
-    if switch is not None:
-        env["SSDK_DENSE_TRAIN"] = switch
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"), cfg=os.path.join(ROOT, "experiments", "cfgs", cfg_name), sync=sync)
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return [int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:]], out.stdout
+    return run_solver_script(_SOLVER, cfg_name, env={"SSDK_DENSE_TRAIN": switch}, text=True, sync=sync)
 
 
 @pytest.mark.parametrize("switch", [None, "0", "1"])

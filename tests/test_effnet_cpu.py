@@ -5,7 +5,6 @@ planner's walk and the training Solver's routing."""
 import ctypes
 import os
 import subprocess
-import sys
 
 import pytest
 import torch
@@ -13,6 +12,7 @@ import torch
 import cases_effnet
 import mbseaudit
 import nethelp
+from solverhelp import run_solver_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["EfficientNetB%d" % i for i in range(6)]
@@ -291,8 +291,6 @@ def test_wider_stems_are_reported_not_planned():
 
 # ---- 7. the training Solver ----------------------------------------------------------------------------------------------------
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 from ssds.core import config
 from ssds.utils import train_ddp
 import torch.nn as nn
@@ -306,9 +304,5 @@ print("RESULT", len(dw5), sum(type(m) is PlainConv2d for m in dw5), len(se), sum
 
 
 def test_solver_builds_and_leaves_the_new_layer_types_to_torch():
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"),
-                          cfg=os.path.join(ROOT, "experiments", "cfgs", "bifpn_efficientnetb0_512.yml"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    n5, plain5, nse, plainse = [int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:]]
+    n5, plain5, nse, plainse = run_solver_script(_SOLVER, "bifpn_efficientnetb0_512.yml")
     assert n5 == plain5 == 9 and nse == plainse == 32  # B0: 2 + 3 + 4 blocks with 5x5 windows; 16 blocks x 2 SE convolutions

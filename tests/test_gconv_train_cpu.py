@@ -2,10 +2,10 @@
 that need no GPU: the layout of the input-gradient weights, which layers of the registered backbones ``use_native_gconv``
 swaps, the argument checks of the C entry points, and the Solver's switch."""
 import os
-import subprocess
-import sys
 
 import pytest
+
+from solverhelp import run_solver_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -165,8 +165,6 @@ def test_c_entry_points_are_exported_and_refuse_bad_arguments():
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 from ssds.core import config
 from ssds.utils import train_ddp
 from ssds.modeling.layers import groupedconv as G
@@ -183,15 +181,7 @@ print("RESULT", len(grouped), sum(type(m) is G.GroupedConv3x3 for m in grouped),
 def test_solver_switch(cfg_name, switch):
     """train_ddp.Solver routes the grouped layers of the two grouped configs natively unless SSDK_GCONV_TRAIN=0 (read when the
     Solver is built; a subprocess per value)."""
-    env = dict(os.environ)
-    env.pop("SSDK_GCONV_TRAIN", None)
-    if switch is not None:
-        env["SSDK_GCONV_TRAIN"] = switch
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"), cfg=os.path.join(ROOT, "experiments", "cfgs", cfg_name))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    line = [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()
-    total, native, swapped = int(line[1]), int(line[2]), int(line[3])
+    total, native, swapped = run_solver_script(_SOLVER, cfg_name, env={"SSDK_GCONV_TRAIN": switch})
     assert total > 0
     if switch == "0":
         assert native == 0 and swapped == 0

@@ -4,13 +4,12 @@ SSDK_MBCONV_TRAIN, a swapped block on CPU tensors, the depth conditions of tests
 fp32 model of every pass and on planted defects."""
 import copy
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
 import mbconvjudge as J
+from solverhelp import run_solver_script
 
 ROOT = J.ROOT
 NEW = ("ssdk_dwconv5_fwd", "ssdk_dwconv5_bwd_data", "ssdk_dwconv5_bwd_weight", "ssdk_dwconv5_bwd_weight_workspace_bytes",
@@ -115,8 +114,6 @@ def test_supported_is_true_for_every_block(name):
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 from ssds.core import config
 from ssds.modeling import model_builder
 from ssds.utils import train_ddp
@@ -140,15 +137,7 @@ print("RESULT", len(blocks), sum(type(b) is M.TrainMBConvBlock for b in blocks),
 def test_solver_routing(switch):
     from ssds.modeling.layers import mbconvtrain as M
 
-    env = dict(os.environ)
-    env.pop("SSDK_MBCONV_TRAIN", None)
-    if switch is not None:
-        env["SSDK_MBCONV_TRAIN"] = switch
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"),
-                          cfg=os.path.join(ROOT, "experiments", "cfgs", "bifpn_efficientnetb0_512.yml"))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    blocks, swapped, same, convs, want_convs, stat = (int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:])
+    blocks, swapped, same, convs, want_convs, stat = run_solver_script(_SOLVER, "bifpn_efficientnetb0_512.yml", env={"SSDK_MBCONV_TRAIN": switch})
     on = (M.DEFAULT if switch is None else switch) != "0"
     assert blocks == 16 and same == 1 and convs == want_convs == 9 + 2 * 16
     assert (swapped, stat) == ((16, 16) if on else (0, 0))

@@ -4,10 +4,10 @@ tensors, which modules ``use_native_neck`` switches on the four FPN / BiFPN conf
 what the unflagged one does on the CPU, and the Solver's routing under SSDK_NECK_TRAIN."""
 import copy
 import os
-import subprocess
-import sys
 
 import pytest
+
+from solverhelp import run_solver_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -232,8 +232,6 @@ def test_flagged_model_equals_the_unflagged_one_on_cpu(kind):
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 import torch.nn as nn
 from ssds.core import config
 from ssds.utils import train_ddp
@@ -252,14 +250,7 @@ print("RESULT", len(bifpn), sum(m.native_neck for m in bifpn), int(isinstance(s.
 
 
 def _solver(cfg_name, switch):
-    env = dict(os.environ)
-    env.pop("SSDK_NECK_TRAIN", None)
-    if switch is not None:
-        env["SSDK_NECK_TRAIN"] = switch
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"), cfg=os.path.join(ROOT, "experiments", "cfgs", cfg_name))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return [int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:]]
+    return run_solver_script(_SOLVER, cfg_name, env={"SSDK_NECK_TRAIN": switch})
 
 
 @pytest.mark.parametrize("cfg_name", ["fpn_resnet50_640.yml", "bifpn_regnetx008_896.yml"])

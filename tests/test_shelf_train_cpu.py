@@ -5,10 +5,10 @@ takes, that a swapped model computes bit for bit what the unswapped one does on 
 Shelf config.  The kernels themselves are checked on the GPU in tests/test_gpu_shelf_train.py."""
 import copy
 import os
-import subprocess
-import sys
 
 import pytest
+
+from solverhelp import run_solver_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ssdk_convt_train_prepare", "ssdk_convt_train_forward", "ssdk_convt_train_dgrad", "ssdk_convt_train_wgrad_workspace_bytes",
@@ -204,8 +204,6 @@ def test_cpu_fp32_and_strided_operands_raise_in_the_explicit_call():
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 import torch.nn as nn
 from ssds.core import config
 from ssds.utils import train_ddp
@@ -220,14 +218,8 @@ print("RESULT", sum(type(m) is CT.ShelfConvT for m in mods), CT.STATS["swapped"]
 
 
 def _solver(cfg_name, **switches):
-    env = dict(os.environ)
-    for k in ("SSDK_CONVT_TRAIN", "SSDK_CAT_TRAIN", "SSDK_DENSE3_TRAIN", "SSDK_NECK_TRAIN", "SSDK_CONV3_NATIVE"):
-        env.pop(k, None)
-    env.update(switches)
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"), cfg=os.path.join(ROOT, "experiments", "cfgs", cfg_name))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return [int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:]]
+    unset = dict.fromkeys(("SSDK_CONVT_TRAIN", "SSDK_CAT_TRAIN", "SSDK_DENSE3_TRAIN", "SSDK_NECK_TRAIN", "SSDK_CONV3_NATIVE"))
+    return run_solver_script(_SOLVER, cfg_name, env=dict(unset, **switches))
 
 
 @pytest.mark.parametrize("setting", ["defaults", "on", "off"])

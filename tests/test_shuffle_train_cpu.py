@@ -4,13 +4,12 @@ of the padded weight images, which modules ``use_native_shuffle`` flags, swaps a
 bit what the unflagged one does on the CPU, the Solver's routing, and the channel arithmetic of a slice."""
 import copy
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import shufflejudge as SJ
+from solverhelp import run_solver_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ssdk_pws_prepare", "ssdk_pws_stats_workspace_bytes", "ssdk_pws_forward", "ssdk_pws_wgrad_workspace_bytes", "ssdk_pws_wgrad",
@@ -218,8 +217,6 @@ def test_slice_arithmetic_matches_torch_strides(shape, cb):
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 import torch.nn as nn
 from ssds.core import config
 from ssds.utils import train_ddp
@@ -237,14 +234,7 @@ print("RESULT", sum(bool(getattr(m, "native_shuffle", False)) for m in mods), ST
 
 
 def _solver(cfg_name, switch):
-    env = dict(os.environ)
-    env.pop("SSDK_SHUFFLE_TRAIN", None)
-    if switch is not None:
-        env["SSDK_SHUFFLE_TRAIN"] = switch
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"), cfg=os.path.join(ROOT, "experiments", "cfgs", cfg_name))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return [int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:]]
+    return run_solver_script(_SOLVER, cfg_name, env={"SSDK_SHUFFLE_TRAIN": switch})
 
 
 @pytest.mark.parametrize("switch", [None, "0", "1"])

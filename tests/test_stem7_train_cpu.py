@@ -10,6 +10,8 @@ import sys
 
 import pytest
 
+from solverhelp import run_solver_script
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NEW = ("ssdk_stem7x7s2_wgrad_workspace_bytes", "ssdk_stem7x7s2_fwd", "ssdk_stem7x7s2_wgrad")
@@ -123,8 +125,6 @@ def test_c_entry_points_are_exported_and_refuse_bad_arguments():
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 import torch.nn as nn
 from ssds.core import config
 from ssds.utils import train_ddp
@@ -137,17 +137,6 @@ print("RESULT", len(sevens), sum(type(m) is S.StemConv7x7s2 for m in mods), sum(
 """
 
 
-def _solver(cfg_name, switch):
-    env = dict(os.environ)
-    env.pop("SSDK_STEM7_TRAIN", None)
-    if switch is not None:
-        env["SSDK_STEM7_TRAIN"] = switch
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"), cfg=os.path.join(ROOT, "experiments", "cfgs", cfg_name))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return [int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:]]
-
-
 @pytest.mark.parametrize("cfg_name,stems", [("fpn_resnext50_640.yml", 1), ("bifpn_regnetx016_896.yml", 0)])
 @pytest.mark.parametrize("switch", [None, "1", "0"])
 def test_solver_routing(cfg_name, stems, switch):
@@ -155,7 +144,7 @@ def test_solver_routing(cfg_name, stems, switch):
     built; a subprocess per value; unset is stemconv.DEFAULT); with 0 the layer stays a plain nn.Conv2d; a RegNetX model has none."""
     from ssds.modeling.layers import stemconv as S
 
-    sevens, native, plain, swapped = _solver(cfg_name, switch)
+    sevens, native, plain, swapped = run_solver_script(_SOLVER, cfg_name, env={"SSDK_STEM7_TRAIN": switch})
     assert sevens == stems
     on = (S.DEFAULT if switch is None else switch) != "0"
     if on:

@@ -4,10 +4,10 @@ explicit functions do with CPU tensors, which modules ``use_native_cat`` flags, 
 unflagged one does on the CPU, and the Solver's routing of the two shipped YOLO configs."""
 import copy
 import os
-import subprocess
-import sys
 
 import pytest
+
+from solverhelp import run_solver_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ssdk_cat_train_fwd", "ssdk_cat_train_bwd", "ssdk_spp_train_fwd", "ssdk_spp_train_bwd")
@@ -186,8 +186,6 @@ def test_use_native_cat_leaves_other_spp_blocks_alone():
 
 
 _SOLVER = r"""
-import sys, torch
-sys.path[:0] = [%(root)r, %(pkg)r]
 import torch.nn as nn
 from ssds.core import config
 from ssds.utils import train_ddp
@@ -202,14 +200,8 @@ print("RESULT", plain3, sum(bool(getattr(m, "native_cat", False)) for m in mods)
 
 
 def _solver(cfg_name, **switches):
-    env = dict(os.environ)
-    for k in ("SSDK_CAT_TRAIN", "SSDK_DENSE3_TRAIN", "SSDK_NECK_TRAIN", "SSDK_CONV3_NATIVE"):
-        env.pop(k, None)
-    env.update(switches)
-    code = _SOLVER % dict(root=ROOT, pkg=os.path.join(ROOT, "ssds.pytorch_amd"), cfg=os.path.join(ROOT, "experiments", "cfgs", cfg_name))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return [int(v) for v in [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()[1:]]
+    unset = dict.fromkeys(("SSDK_CAT_TRAIN", "SSDK_DENSE3_TRAIN", "SSDK_NECK_TRAIN", "SSDK_CONV3_NATIVE"))
+    return run_solver_script(_SOLVER, cfg_name, env=dict(unset, **switches))
 
 
 @pytest.mark.parametrize("cfg_name", ["yolov3_resnet18_320.yml", "yolov4_resnet18_512.yml"])

@@ -135,37 +135,16 @@ if world > 1:
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t)
 if rank == 0:
-    from ssds.modeling.layers import denseconv as _D
+    from ssds.modeling import train_routing
 
-    _dense3 = _D.STATS["swapped"] > 0  # SSDK_DENSE3_TRAIN routed the dense 3x3 layers of this (FPN / BiFPN) model natively
-    from ssds.modeling.layers import neckfuse as _NF
-
-    _neck = _NF.STATS["fuse_forward"] + _NF.STATS["pool_forward"] > 0  # SSDK_NECK_TRAIN: the fusions / top-down adds / stem pool ran natively
-    from ssds.modeling.layers import stemconv as _S7
-
-    _stem7 = _S7.STATS["native_forward"] > 0  # SSDK_STEM7_TRAIN: the 7x7 stem of a ResNet / ResNeXt backbone ran natively
-    from ssds.modeling.layers import mbconvtrain as _MB
-
-    _mbconv = _MB.STATS["native_forward"] > 0  # SSDK_MBCONV_TRAIN: the EfficientNet MBConv blocks ran their 5x5 depthwise / SiLU + squeeze-excite natively
-    from ssds.modeling.layers import cattrain as _CT
-
-    _cat = _CT.STATS["cat_forward"] + _CT.STATS["spp_forward"] > 0  # SSDK_CAT_TRAIN: the concatenations / SPP block of a YOLO model ran natively
-    from ssds.modeling.layers import convttrain as _CV
-
-    _convt = _CV.STATS["native_forward"] > 0  # SSDK_CONVT_TRAIN: the transposed convolutions of a Shelf model ran natively
-    from ssds.modeling.layers import shuffletrain as _ST
-
-    _shuffle = _ST.STATS["join_forward"] > 0  # SSDK_SHUFFLE_TRAIN: the units of a ShuffleNetV2 backbone ran their slice 1x1 / join natively
-    from ssds.modeling.layers import densetrain as _DT
-
-    _dense = _DT.STATS["native_forward"] > 0  # SSDK_DENSE_TRAIN: the dense blocks of a DenseNet backbone ran on one buffer
     _name = "SSD-MobileNetV2" if args.cfg == "ssd_mobilenetv2_512.yml" else "%s-%s" % (cfg.MODEL.SSDS, cfg.MODEL.NETS)
-    print(json.dumps({"metric": "images/sec (DDP training step) %s@%d" % (_name, cfg.MODEL.IMAGE_SIZE[0]), "value": round(world * args.batch * args.steps / el, 1),
-                      "n_gpus": world, "ms_per_step": round(el / args.steps * 1e3, 2), "batch_per_gpu": args.batch,
-                      "cls_loss": float(c), "loc_loss": float(l), "dtype": "bf16 autocast", "hipgraph": bool(args.graph), "sync_bn": bool(args.sync_bn),
-                      "optimizer": args.optimizer, "cfg": args.cfg, "gconv_train": os.environ.get("SSDK_GCONV_TRAIN", "1") != "0",
-                      "dense3_train": _dense3, "neck_train": _neck, "stem7_train": _stem7, "mbconv_train": _mbconv, "cat_train": _cat, "convt_train": _convt, "shuffle_train": _shuffle, "dense_train": _dense,
-                      "peak_allocated_MiB": None if args.cpu else round(torch.cuda.max_memory_allocated() / 2 ** 20, 1),
-                      "data": "synthetic" if not args.cpu else "stub (CPU / gloo run of the rank logic)"}))
+    line = {"metric": "images/sec (DDP training step) %s@%d" % (_name, cfg.MODEL.IMAGE_SIZE[0]), "value": round(world * args.batch * args.steps / el, 1),
+            "n_gpus": world, "ms_per_step": round(el / args.steps * 1e3, 2), "batch_per_gpu": args.batch,
+            "cls_loss": float(c), "loc_loss": float(l), "dtype": "bf16 autocast", "hipgraph": bool(args.graph), "sync_bn": bool(args.sync_bn),
+            "optimizer": args.optimizer, "cfg": args.cfg}
+    line.update(train_routing.bench_fields())  # "<family>_train": the kernels of that entry of the Solver's routing table ran in this process
+    line.update({"peak_allocated_MiB": None if args.cpu else round(torch.cuda.max_memory_allocated() / 2 ** 20, 1),
+                 "data": "synthetic" if not args.cpu else "stub (CPU / gloo run of the rank logic)"})
+    print(json.dumps(line))
 if world > 1:
     dist.destroy_process_group()
