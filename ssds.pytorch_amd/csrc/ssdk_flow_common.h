@@ -24,6 +24,7 @@ struct FlowParams {
   const float* bp;
   int N, H, W, Cin, Chid, Cout, Ho, Wo, residual;
   int strips, segs, rs;  // strips per row, row segments per image, output rows per segment
+  int strip_layout;      // ssdk_flow_plan.h FlowLayout: which columns a strip holds and which of its lanes store
   // STEM instances: x is the image [N][Cimg<=3][Himg][Wimg] (layout 1, NCHW) or [N][Himg][Wimg][Cimg] (2, NHWC); the
   // "expand" GEMM is the 3x3 / stride 2 / pad 1 stem convolution, K = (ci, ky, kx) = 27 of 32; H, W = its output grid
   int Himg, Wimg, Cimg, layout;
@@ -65,7 +66,8 @@ template <int DT> __device__ __forceinline__ float fl_from16(u32 h) {
   if constexpr (DT == SSDK_BF16) return bf16_bits_to_f32(h);
   else return f16_bits_to_f32(h);
 }
-// neighbour pixel inside the 16-lane row; the row's first / last lane gets 0 (those lanes are halo pixels)
+// neighbour pixel inside the 16-lane row; the row's first / last lane gets 0 (those lanes are halo pixels, or columns 0 / W - 1
+// of the map, whose missing neighbour is the zero padding: ssdk_flow_plan.h)
 __device__ __forceinline__ u32 fl_from_left(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true); }   // row_shr:1
 __device__ __forceinline__ u32 fl_from_right(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true); }  // row_shl:1
 

@@ -37,6 +37,7 @@
 
 #include "ssdk_common.h"
 #include "ssdk_flow_common.h"
+#include "ssdk_flow_plan.h"
 
 namespace ssdk {
 
@@ -188,16 +189,18 @@ __global__ __launch_bounds__(kFlowThreads, ((STEM && !YE) || PAIR) ? 3 : 2) void
   const int oy0 = seg * p.rs, oy1 = (oy0 + p.rs < p.Ho ? oy0 + p.rs : p.Ho) - 1;  // output rows [oy0, oy1]
   int ix[NS], oxl[NA];
   bool col_ok[NS], out_lane[NA];
+  const int layout = STEM ? (int)kFlowHalo : p.strip_layout;  // columns of a strip, lanes that store (stride 1; ssdk_flow_plan.h)
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     const int strip = grp * NS + s;
     const int ox0 = strip * OW;
-    ix[s] = MERGE ? 2 * (grp * 15 + (int)fr) - s : ox0 * S - 1 + (int)fr;  // this lane's input column in strip s
+    // this lane's input column in strip s
+    ix[s] = MERGE ? 2 * (grp * 15 + (int)fr) - s : S == 1 ? flow_strip_col0(layout, strip) + (int)fr : ox0 * S - 1 + (int)fr;
     col_ok[s] = strip < p.strips && (unsigned)ix[s] < (unsigned)p.W;
     if constexpr (!MERGE) {
-      // output pixel of this lane (if any): stride 1: lanes 1..14, stride 2: odd lanes 1..13
-      oxl[s] = S == 1 ? ox0 + (int)fr - 1 : ox0 + ((int)fr - 1) / 2;
-      out_lane[s] = strip < p.strips && (S == 1 ? (fr >= 1u && fr <= 14u) : ((fr & 1u) && fr <= 13u)) && oxl[s] < p.Wo;
+      // output pixel of this lane (if any): stride 1: its own column where the layout lets the lane store, stride 2: odd lanes 1..13
+      oxl[s] = S == 1 ? ix[s] : ox0 + ((int)fr - 1) / 2;
+      out_lane[s] = strip < p.strips && (S == 1 ? flow_lane_stores(layout, strip, (int)fr, p.Wo) : ((fr & 1u) && fr <= 13u && oxl[s] < p.Wo));
     }
   }
   if constexpr (MERGE) {  // lane j <= 14: output grp * 15 + j (lane 15 has no right tap)
@@ -282,7 +285,7 @@ __global__ __launch_bounds__(kFlowThreads, ((STEM && !YE) || PAIR) ? 3 : 2) void
     if constexpr (STEM) {
       const int strip = grp * NS + s;
       // element offset of (image row 2iy-1, image column 2*ix-1 of the strip's lane 0, channel 0)
-      const int base = ((2 * iy - 1) * p.Wimg + (2 * (strip * 14 - 1) - 1)) * pstr;
+      const int base = ((2 * iy - 1) * p.Wimg + (2 * flow_strip_col0(kFlowHalo, strip) - 1)) * pstr;
       if constexpr (XD) {
         const bool row_in = (unsigned)iy < (unsigned)p.H, top = iy == 0;  // wave-uniform
         const int soff = row_in ? (base + 1) * 2 + xmargin - 4 : (int)kOOR;  // (column 2 ix of the strip's lane 0; pstr == 1)
@@ -765,13 +768,18 @@ __global__ __launch_bounds__(kFlowThreads, ((STEM && !YE) || PAIR) ? 3 : 2) void
 
 constexpr int kFlowNS = 2;  // strips per wave
 
+// SSDK_FLOW_PAIR (docs/SWITCHES.md): the one-strip instance walks its rows in pairs (default) or one by one
+static bool flow_pair_env() {
+  static const int pair = getenv("SSDK_FLOW_PAIR") ? atoi(getenv("SSDK_FLOW_PAIR")) : 1;
+  return pair != 0;
+}
+
 template <int DT, int S, int NCH, int NFO>
 static void flow_launch(const FlowParams& p, unsigned grid, hipStream_t stream) {
   constexpr int lds = FlowLds<NCH, NFO>::bytes;
   if constexpr (S == 1 && NCH == 9) {
     if (p.layout == 101) {  // one strip per wave (launch_mbflow sets the marker: half the accumulators, three waves per SIMD)
-      static const int pair = getenv("SSDK_FLOW_PAIR") ? atoi(getenv("SSDK_FLOW_PAIR")) : 1;
-      if (pair) {  // two input rows per visit of the chunks: every weight read serves two rows
+      if (flow_pair_env()) {  // two input rows per visit of the chunks: every weight read serves two rows
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mbflow_kernel<DT, S, NCH, NFO, 1, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipLaunchKernelGGL((mbflow_kernel<DT, S, NCH, NFO, 1, false, false, true>), dim3(grid), dim3(kFlowThreads), lds, stream, p);
         return;
@@ -862,11 +870,9 @@ int launch_mbflow(const ssdk_mbconv_desc* d, hipStream_t stream) {
       fprintf(stderr, " [%llu %llu %llu %llu]", hh[i + 1] - hh[i], hh[i + 2] - hh[i + 1], hh[i + 3] - hh[i + 2], hh[i + 4] - hh[i + 3]);
     fprintf(stderr, "\n");
   };
-  const int ow = d->stride == 1 ? 14 : 7;
-  p.strips = (p.Wo + ow - 1) / ow;
-  if (d->stride == 2) p.strips = 2 * ((p.Wo + 14) / 15);  // parity split: a pair of strips = 15 outputs (even / odd input columns)
-  // rows per segment: long segments amortise the two halo rows, short ones give the chip enough waves (>= ~3 per SIMD)
-  constexpr int env_rs = 0;  // (round 6: the SSDK_MB_FLOW_RS switch is gone, its A/B is settled)
+  // the cut of the map into strips and row segments: ssdk_flow_plan.h
+  p.strip_layout = flow_layout(d->stride, stem);
+  p.strips = flow_strips(p.strip_layout, p.Wo);
   // strips per wave: two share every weight read, but the 144-channel stride-1 block then holds 216 registers (3 x 2 x 18
   // accumulators): two waves per SIMD.  With ONE strip it holds 132 -- three waves per SIMD -- and runs 125 -> 114 us (round 4,
   // same box; forcing 128 registers for a fourth wave spills and gives the gain back: 121 us).  The stem block (NCH = 2) does not
@@ -875,21 +881,26 @@ int launch_mbflow(const ssdk_mbconv_desc* d, hipStream_t stream) {
   const bool ns1 = ((env_ns1 & 1) && !stem && d->stride == 1 && nch == 9) || ((env_ns1 & 2) && stem);
   const int flow_ns = ns1 ? 1 : kFlowNS;
   if (ns1 && !stem) p.layout = 101;
-  const int groups = (p.strips + flow_ns - 1) / flow_ns;
-  // (measured: ~5000 items of 16-32 rows beat ~2500 of 32-64 rows; below 16 rows the two halo rows of a segment cost
-  //  too much, and a map that then yields fewer than 2048 items -- 64x64 at batch 64 -- stays with the LDS-tiled kernel)
-  int rs = 64;
-  while (rs > 16 && (long)d->N * groups * ((p.Ho + rs - 1) / rs) < 4096) rs >>= 1;
-  if ((long)d->N * groups * ((p.Ho + rs - 1) / rs) < 2048 && env_rs <= 0 && variant <= 0) return 1;
-  if (variant > 0) {  // forced (tests): short segments so that small maps still exercise several segments
-    while (rs > 8 && (long)d->N * groups * ((p.Ho + rs - 1) / rs) < 2048) rs >>= 1;
+  const int groups = flow_groups(p.strips, flow_ns);
+  // rows per segment: the lengths on offer are those the row loop runs without surplus rows, and the one is taken that leaves
+  // the busiest SIMD the fewest rows (flow_plan_rows; the stem instances keep 64 / 32 / 16 rows).  A map that yields fewer than
+  // 2048 items of 16 rows -- 64x64 at batch 64 -- stays with the LDS-tiled kernel; a forced launch (tests) takes short
+  // segments, so that small maps still exercise several.
+  const bool pair = ns1 && !stem && flow_pair_env();
+  const long per_row = (long)d->N * groups;
+  if (!flow_takes(per_row, p.Ho) && variant <= 0) return 1;
+  static int simds = 0;
+  if (!simds) {
+    int dev = 0, cus = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    simds = 4 * cus;
   }
-  if (env_rs > 0) rs = env_rs;
-  if (rs > p.Ho) rs = p.Ho;
-  p.rs = rs;
-  p.segs = (p.Ho + rs - 1) / rs;
-  const long items = (long)d->N * groups * p.segs;
-  const unsigned grid = (unsigned)((items + 3) / 4);
+  const FlowRows rows = stem ? flow_plan_rows_halving(per_row, p.Ho, variant > 0)
+                             : flow_plan_rows(per_row, p.Ho, d->stride, pair, variant > 0, simds);
+  p.rs = rows.rs;
+  p.segs = rows.segs;
+  const unsigned grid = (unsigned)((rows.items + 3) / 4);
   bool ok;
   if (stem) {
     // The interior instance copes with everything above the image and with rows outside the block's grid; only a real

@@ -438,6 +438,7 @@ int launch_mbsplit(const ssdk_mbconv_desc* d, hipStream_t stream) {
   p.Wimg = d->W;
   p.Cimg = d->Cin;
   p.layout = 0;
+  p.strip_layout = 0;  // (ssdk_mbflow.hip's; this kernel has one layout)
   p.Chid = d->Chid;
   p.Cout = d->Cout;
   p.Ho = (p.H + 2 - 3) / d->stride + 1;
