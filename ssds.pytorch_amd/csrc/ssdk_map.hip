@@ -15,12 +15,9 @@
 //                    running maximum from the right (the VOC envelope), summed at the ranks where recall moves.
 //
 // Sorting the records (once per epoch) is left to the caller (rocPRIM radix sort through torch.sort).
-#include "ssdk_common.h"
+#include "ssdk_map.h"
 
 namespace ssdk {
-
-constexpr int kMapThreads = 256;
-constexpr int kMapPer = 8;  // detections per thread: D <= kMapThreads * kMapPer
 
 struct MapParams {
   const float* scores;   // [B, D]
@@ -64,11 +61,7 @@ __global__ __launch_bounds__(kMapThreads) void map_match_kernel(const MapParams 
     int bg = -1;
     for (int g = 0; g < p.G; ++g) {
       if (gt[g][4] != c) continue;  // evaluation_metrics.py:33
-      const float lx = fmaxf(x1, gt[g][0]), ly = fmaxf(y1, gt[g][1]);  // :20-21
-      const float rx = fminf(x2, gt[g][2]), ry = fminf(y2, gt[g][3]);
-      const float inter = (lx < rx && ly < ry) ? (rx - lx) * (ry - ly) : 0.f;  // :23
-      const float area_b = (gt[g][2] - gt[g][0]) * (gt[g][3] - gt[g][1]);      // :25
-      const float iou = inter / (area_a + area_b - inter);                     // :26
+      const float iou = map_iou(x1, y1, x2, y2, area_a, gt[g]);  // :20-26
       if (bg < 0 || iou > best) {  // :49 argmax, first maximum
         best = iou;
         bg = g;
@@ -108,34 +101,8 @@ __global__ __launch_bounds__(64) void map_ap_kernel(const unsigned char* tp, con
     if (lane == 0) ap[c] = __builtin_nan("");
     return;
   }
-  const double dnp = (double)np;
-  long long T = 0;
-  for (long long j = 0; j < n; j += 64) {
-    const bool t = (j + lane < n) && tp[s0 + j + lane] != 0;
-    T += __popcll(__ballot(t));
-  }
-  double carry = 0.0, acc = 0.0;
-  long long tp_ge = 0;  // true positives at ranks >= the current chunk
-  for (long long j = ((n - 1) / 64) * 64; j >= 0 && n > 0; j -= 64) {
-    const bool in = j + lane < n;
-    const bool t = in && tp[s0 + j + lane] != 0;
-    const u64 m = __ballot(t);
-    tp_ge += __popcll(m);
-    const long long tpj = (T - tp_ge) + (long long)__popcll(m & ((lane == 63u) ? ~0ull : ((2ull << lane) - 1ull)));
-    // :136-137  prec = tp / max(tp + fp, eps) with tp + fp = rank + 1
-    double pr = in ? (double)tpj / (double)(j + lane + 1) : 0.0;
-    pr = pr > carry ? pr : carry;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {  // suffix maximum across the wave (:104-106)
-      const double o = __shfl_down(pr, d);
-      if (lane + d < 64u) pr = pr > o ? pr : o;
-    }
-    carry = __shfl(pr, 0);
-    // :108-111  recall moves exactly at the true positives
-    if (t) acc += ((double)tpj / dnp - (double)(tpj - 1) / dnp) * pr;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+  const unsigned char* t = tp + s0;
+  const double acc = map_envelope_sum(n, lane, [t](long long j) { return t[j] != 0; }, MapVocWeight{(double)np});
   if (lane == 0) ap[c] = acc;
 }
 

@@ -7,11 +7,75 @@ The reference loops over images x classes in Python and appends to per-class lis
 one radix sort of the epoch's records plus one launch (``ssdk_map_average_precision``).  Nothing returns to the host
 before ``get_results``.  Tie contract: among same-class boxes of equal IoU the first wins (``argmax`` on CPU);
 detections of equal score keep their arrival order (the reference's ``np.argsort(...)[::-1]`` leaves it undefined).
-The numpy-2 breakage of the reference (``np.float`` / ``np.NAN``, :90, :126) does not apply."""
+The numpy-2 breakage of the reference (``np.float`` / ``np.NAN``, :90, :126) does not apply.
+
+``AveragePrecisionSweep`` is the same bookkeeping over several IoU thresholds at once (``ssdk_apsweep_match`` /
+``ssdk_apsweep_average_precision``, include/ssdk_apsweep.h): the number quoted for COCO-shaped data, AP averaged over IoU
+0.50 ... 0.95, under pycocotools' greedy rule -- or the reference's rule at every threshold.  Both classes ``merge()`` their
+records over the ranks of a process group at the end of an epoch (``merge_records``)."""
+import ctypes
+
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from ssds import _native as N
+
+COCO_IOUS = np.linspace(0.5, 0.95, 10).astype(np.float32)  # 0.50 : 0.05 : 0.95 as the fp32 values the kernel compares with
+
+
+def merge_records(keys, tp, npos, group=None):
+    """The records of every rank of ``group``, on every rank: ``keys`` [n] int64 and ``tp`` [n] (flags or masks) of this rank are
+    padded to the longest rank's length with sentinel records (key class = num_classes = ``npos.numel()``, flag 0: they sort
+    behind every class, like the padded slots of a batch), all-gathered and concatenated in rank order; ``npos`` [C] is
+    sum-reduced.  -> (keys, tp, npos) on the device of ``keys``, identical on all ranks.  The collectives run on the tensors'
+    device where the backend can (RCCL), else staged through the host (gloo).  Run it once, at the end of an epoch: it
+    synchronises.
+
+    The result equals a one-process evaluation of the same images whenever no two detections of a class have equal scores:
+    records of equal key keep their arrival order under the stable sort, and that order becomes rank-major here."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return keys, tp, npos
+    world, dev = dist.get_world_size(group), keys.device
+    on_device = keys.is_cuda and dist.get_backend(group) == "nccl"
+    if not on_device:
+        keys, tp, npos = keys.cpu(), tp.cpu(), npos.cpu()
+    keys, tp, npos = keys.contiguous().view(-1), tp.contiguous().view(-1), npos.clone()
+    n = torch.tensor([keys.numel()], dtype=torch.int64, device=keys.device)
+    counts = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(counts, n, group=group)
+    longest = max(int(c) for c in counts)
+    sentinel = (int(npos.numel()) << 32) | 0xFFFFFFFF
+    pk = torch.full((longest,), sentinel, dtype=torch.int64, device=keys.device)
+    pt = torch.zeros((longest,), dtype=tp.dtype, device=keys.device)
+    pk[:keys.numel()] = keys
+    pt[:tp.numel()] = tp
+    all_k = [torch.empty_like(pk) for _ in range(world)]
+    all_t = [torch.empty_like(pt) for _ in range(world)]
+    dist.all_gather(all_k, pk, group=group)
+    dist.all_gather(all_t, pt, group=group)
+    dist.all_reduce(npos, op=dist.ReduceOp.SUM, group=group)
+    return torch.cat(all_k).to(dev), torch.cat(all_t).to(dev), npos.to(dev)
+
+
+def _merge_into(metric, tp_dtype, group):
+    """``merge()`` of both metric classes: this rank's records replaced by those of all ranks.  A rank that saw no batch joins
+    the collectives with no records."""
+    if metric._npos is None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        metric._npos = torch.zeros(metric.num_classes, device=dev, dtype=torch.int32)
+    dev = metric._npos.device
+    keys = torch.cat(metric._keys) if metric._keys else torch.empty(0, dtype=torch.int64, device=dev)
+    tp = torch.cat(metric._tp) if metric._tp else torch.empty(0, dtype=tp_dtype, device=dev)
+    keys, tp, metric._npos = merge_records(keys, tp, metric._npos, group)
+    metric._keys, metric._tp = [keys], [tp]
+
+
+def _sort_records(keys, tp, num_classes):
+    """One stable radix sort of an epoch's records -> (sorted keys, tp in that order, the start of every class [C + 1])."""
+    skeys, order = torch.sort(keys, stable=True)  # rocPRIM radix sort
+    bounds = torch.arange(num_classes + 1, device=keys.device, dtype=torch.int64) << 32
+    return skeys, tp[order].contiguous(), torch.searchsorted(skeys, bounds).contiguous()
 
 
 class MeanAveragePrecision(object):
@@ -77,6 +141,11 @@ class MeanAveragePrecision(object):
             precision.append(cum.astype(float) / np.arange(1, len(cum) + 1, dtype=float))
         return mAP, (precision, recall, ap_h.tolist())
 
+    def merge(self, group=None):
+        """End of an epoch under data parallelism: afterwards every rank holds the records of all ranks (``merge_records``;
+        equal to a one-process evaluation whenever no two detections of a class have equal scores)."""
+        _merge_into(self, torch.uint8, group)
+
     def records(self):
         """Per class, in arrival order: (scores, detect_ismatched) and the ground-truth counts -- the reference's
         ``self.score`` / ``self.detect_ismatched`` / ``self.npos`` (:10-13), for tests."""
@@ -87,3 +156,91 @@ class MeanAveragePrecision(object):
         score = bits.view(np.float32)
         return ([score[cls == c] for c in range(self.num_classes)], [tp[cls == c] for c in range(self.num_classes)],
                 self._npos.cpu().numpy())
+
+
+class AveragePrecisionSweep(object):
+    """Average precision at every threshold of ``iou_thresholds`` (strictly ascending, in (0, 1], at most ``N.APSWEEP_MAX_T``)
+    from ONE launch per batch and one sort + one launch per epoch.  ``rule``: "coco" -- pycocotools' greedy matching (per class
+    and threshold a detection takes the free box of highest IoU >= t; only the first ``max_dets`` detections of an image by
+    score count) and 101-point interpolation, without crowd / ignore regions and area ranges; "reference" -- the rule and the
+    VOC area of ``MeanAveragePrecision`` at every threshold (``max_dets`` is ignored).  Same ``__call__`` contract as
+    ``MeanAveragePrecision``; nothing returns to the host before ``get_results``."""
+
+    def __init__(self, num_classes, conf_threshold, iou_thresholds=COCO_IOUS, rule="coco", max_dets=100):
+        if rule not in N.AP_RULE:
+            raise ValueError("AveragePrecisionSweep: rule {!r} (one of {})".format(rule, sorted(N.AP_RULE)))
+        self.num_classes = int(num_classes)
+        self.conf_threshold = float(conf_threshold)
+        self.iou_thresholds = np.asarray(iou_thresholds, dtype=np.float32).reshape(-1)
+        self.rule, self.max_dets = rule, int(max_dets)
+        self._thr = (ctypes.c_float * max(len(self.iou_thresholds), 1))(*[float(v) for v in self.iou_thresholds])
+        self._keys, self._tp = [], []
+        self._npos = None
+
+    def __call__(self, detections, targets):
+        """detections = (scores [B,D], boxes [B,D,4] ltrb, classes [B,D]) as returned by ``Decoder``; targets [B,G,5] = ltrb +
+        label (-1 padding).  Appends this batch's records; no host synchronisation.  Under the COCO rule every image's
+        detections are put into descending score order first (stable: a ``Decoder`` output stays as it is)."""
+        scores, boxes, classes = detections
+        N.require_device(scores, "AveragePrecisionSweep")
+        dev = scores.device
+        scores, boxes, classes = (x.contiguous().float() for x in (scores, boxes, classes))
+        if self.rule == "coco":
+            scores, order = torch.sort(scores, dim=1, descending=True, stable=True)
+            classes = torch.gather(classes, 1, order)
+            boxes = torch.gather(boxes, 1, order.unsqueeze(-1).expand(-1, -1, 4)).contiguous()
+        t = targets.to(dev).contiguous().float()
+        B, D = int(scores.shape[0]), int(scores.shape[1])
+        if t.shape[1] == 0:  # a batch without any box: one padding row, so that the pointer is one
+            t = t.new_full((B, 1, 5), -1.0)
+        G = int(t.shape[1])
+        if self._npos is None:
+            self._npos = torch.zeros(self.num_classes, device=dev, dtype=torch.int32)
+        keys = torch.empty((B, D), device=dev, dtype=torch.int64)
+        tp = torch.empty((B, D), device=dev, dtype=torch.int32)
+        with torch.cuda.device(dev):
+            rc = N.lib.ssdk_apsweep_match(scores.data_ptr(), boxes.data_ptr(), classes.data_ptr(), B, D, t.data_ptr(), G,
+                                          self.num_classes, self.conf_threshold, self._thr, len(self.iou_thresholds),
+                                          N.AP_RULE[self.rule], self.max_dets, keys.data_ptr(), tp.data_ptr(),
+                                          self._npos.data_ptr(), N.stream_ptr(dev))
+        N.check(rc, "apsweep_match")
+        self._keys.append(keys.view(-1))
+        self._tp.append(tp.view(-1))
+
+    def merge(self, group=None):
+        """End of an epoch under data parallelism: afterwards every rank holds the records of all ranks (``merge_records``;
+        equal to a one-process evaluation whenever no two detections of a class have equal scores)."""
+        _merge_into(self, torch.int32, group)
+
+    def average_precision(self):
+        """ap [T, C] fp64 on the device (NaN: a class without ground truth): one sort and one launch."""
+        dev = self._npos.device
+        _, tp, seg = _sort_records(torch.cat(self._keys), torch.cat(self._tp), self.num_classes)
+        T, C = len(self.iou_thresholds), self.num_classes
+        ap = torch.empty((T, C), device=dev, dtype=torch.float64)
+        with torch.cuda.device(dev):
+            rc = N.lib.ssdk_apsweep_average_precision(tp.data_ptr(), seg.data_ptr(), self._npos.data_ptr(), C, T,
+                                                      N.AP_RULE[self.rule], ap.data_ptr(), N.stream_ptr(dev))
+        N.check(rc, "apsweep_average_precision")
+        return ap
+
+    def get_results(self):
+        """(mAP, detail): mAP = the mean of the non-NaN entries of ap[T, C] (AP@[.50:.95] with the default thresholds);
+        detail = {"iou_thresholds" [T], "ap" numpy [T, C] (NaN: a class without ground truth), "mAP_per_iou" [T]}."""
+        T, C = len(self.iou_thresholds), self.num_classes
+        if self._npos is None or not self._keys:
+            ap = np.full((T, C), np.nan)
+        else:
+            ap = self.average_precision().cpu().numpy()
+        have = ~np.isnan(ap)
+        per_iou = np.array([ap[t][have[t]].mean() if have[t].any() else np.nan for t in range(T)])
+        mAP = float(ap[have].mean()) if have.any() else float("nan")
+        return mAP, {"iou_thresholds": self.iou_thresholds.copy(), "ap": ap, "mAP_per_iou": per_iou}
+
+    def records(self):
+        """(key class [n] with num_classes where a slot does not count, scores [n], masks [n], npos [C]) in arrival order, as
+        numpy -- for tests."""
+        keys = torch.cat(self._keys).cpu().numpy()
+        u = (~keys & 0xFFFFFFFF).astype(np.uint32)
+        bits = np.where(u & 0x80000000, u & 0x7FFFFFFF, ~u).astype(np.uint32)
+        return (keys >> 32).astype(np.int64), bits.view(np.float32), torch.cat(self._tp).cpu().numpy(), self._npos.cpu().numpy()

@@ -269,14 +269,18 @@ def train_anchor_based_epoch(model, data_loader, optimizer, anchors, epoch, devi
 
 
 @torch.no_grad()
-def eval_anchor_based_epoch(model, data_loader, decoder, anchors, num_classes, device):
+def eval_anchor_based_epoch(model, data_loader, decoder, anchors, num_classes, device, metrics=None):
     """Eval epoch (reference pipeline_anchor_basic.py:150-182 without tqdm/TensorBoard): forward, decode + NMS and the
     mAP bookkeeping all stay on the device; the host sees one number per class at the end.  Returns
-    (mAP, (precision, recall, ap))."""
+    (mAP, (precision, recall, ap)).
+
+    ``metrics``: a sequence of metric objects (``MeanAveragePrecision``, ``AveragePrecisionSweep``) instead of the default
+    one: each is fed every batch, merged over the ranks at the end when a process group of more than one rank is initialised
+    (every rank then holds the result of the whole data set), and the list of their ``get_results()`` is returned."""
     from ssds.core.evaluation_metrics import MeanAveragePrecision
 
     model.eval()
-    metric = MeanAveragePrecision(num_classes, decoder.conf_threshold, decoder.nms_threshold)
+    fed = [MeanAveragePrecision(num_classes, decoder.conf_threshold, decoder.nms_threshold)] if metrics is None else list(metrics)
     for images, targets in data_loader:
         if images.device != device:
             images, targets = images.to(device), targets.to(device)
@@ -284,5 +288,11 @@ def eval_anchor_based_epoch(model, data_loader, decoder, anchors, num_classes, d
         loc, conf = model(images)
         detections = decoder(loc, conf, anchors)
         targets[:, :, 2:4] = targets[:, :, :2] + targets[:, :, 2:4]  # xywh -> ltrb (:175)
-        metric(detections, targets)
-    return metric.get_results()
+        for metric in fed:
+            metric(detections, targets)
+    if metrics is None:
+        return fed[0].get_results()
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        for metric in fed:
+            metric.merge()
+    return [metric.get_results() for metric in fed]
