@@ -8,7 +8,7 @@ import ctypes
 import torch
 
 from ssds import _native as N
-from ssds.modeling.layers.box import _anchor_array
+from ssds.modeling.layers.box import _anchor_array, fit_rows
 
 
 class _MatchLoss(torch.autograd.Function):
@@ -24,7 +24,7 @@ class _MatchLoss(torch.autograd.Function):
         if conf_c.shape[1] != A * classes or tuple(loc_c.shape) != (B, A * 4, H, W):
             raise ValueError("match_loss: conf %s / loc %s do not fit %d anchors x %d classes" % (
                 tuple(conf.shape), tuple(loc.shape), A, classes))
-        t = targets.contiguous().float()
+        t = fit_rows(targets.contiguous().float())  # 1 .. SSDK_MAX_GT rows: [B, 0, 5] and padded batches beyond the limit too
         G = int(t.shape[1])
         dev = conf_c.device
         d_conf, d_loc = torch.empty_like(conf_c), torch.empty_like(loc_c)
@@ -57,9 +57,15 @@ class _MatchLoss(torch.autograd.Function):
     def backward(ctx, g_cls, g_loc, _g_sums):
         d_conf, d_loc = ctx.saved_tensors
         # out of place: the saved gradients stay what the kernel wrote, so backward(retain_graph=True) may run again
-        gc = d_conf * g_cls if g_cls is not None else None  # 0-dim fp32 scale, fp32 arithmetic, dtype kept
-        gl = d_loc * g_loc if g_loc is not None else None
+        # (one pass, fp32 arithmetic, one more store in the gradients' dtype: a 0-dim scale would be rounded to that dtype first on
+        # the device -- up to 2^-9 of every gradient of the level in bf16 -- a 1-element fp32 operand makes fp32 the computation type)
+        gc = _scaled(d_conf, g_cls) if g_cls is not None else None
+        gl = _scaled(d_loc, g_loc) if g_loc is not None else None
         return (gc, gl) + (None,) * 13
+
+
+def _scaled(grad, scale):
+    return torch.mul(grad, scale.reshape(1).float(), out=torch.empty_like(grad))
 
 
 LOC_LOSS = {"smoothl1": 0, "iou": 1, "giou": 2, "diou": 3, "ciou": 4}

@@ -80,6 +80,24 @@ def _anchor_array(anchors, stride=None):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def fit_rows(t):
+    """Ground truth [B, G, 5] (fp32, label -1 = padding) in the 1 .. SSDK_MAX_GT rows per image the matching kernels stage: an
+    empty batch (G = 0, whose tensor has no storage to point at) becomes one padding row; more than SSDK_MAX_GT rows are compacted,
+    valid rows first in their order (the order decides ties, box.py:171 / :320), and cut -- a ValueError names the limit when an
+    image holds more VALID rows than that (the only case that reads the counts back to the host)."""
+    B, G = int(t.shape[0]), int(t.shape[1])
+    if G == 0:
+        return t.new_full((B, 1, 5), -1.0)
+    if G <= N.MAX_GT:
+        return t
+    valid = t[:, :, 4] > -1
+    most = int(valid.sum(1).max())
+    if most > N.MAX_GT:
+        raise ValueError("extract_targets: %d valid ground-truth rows in one image, the kernels take SSDK_MAX_GT = %d" % (most, N.MAX_GT))
+    order = torch.argsort((~valid).to(torch.uint8), dim=1, stable=True)[:, :N.MAX_GT]
+    return torch.gather(t, 1, order.unsqueeze(-1).expand(-1, -1, 5)).contiguous()
+
+
 def extract_targets(
     targets,
     anchors,
@@ -108,7 +126,7 @@ def extract_targets(
     N.require_device(targets, "extract_targets")
     anc = _anchor_array(anchors, stride)
     A = anc.shape[0]
-    t = targets.contiguous().float()
+    t = fit_rows(targets.contiguous().float())
     B, G = int(t.shape[0]), int(t.shape[1])
     H, W = int(size[0]), int(size[1])
     dev = t.device
