@@ -24,11 +24,11 @@ import torch
 import torch.nn as nn
 
 from ssds import _native as N
+from ssds.modeling.layers import kernel_conv as K
 from ssds.modeling.layers import denseconv
 
 MIN_C, MAX_C = 16, 4096  # csrc/ssdk_convttrain.hip ct_check
 STATS = {"swapped": 0, "native_forward": 0, "native_dgrad": 0, "native_wgrad": 0}
-_HALF = (torch.bfloat16, torch.float16)
 
 
 def shape_supported(cin, cout):
@@ -141,9 +141,7 @@ class _ConvT3x3S2(torch.autograd.Function):
         wdt, bdt, cout = ctx.meta
         n, cin, h, wd = (int(v) for v in x.shape)
         dev, dt = x.device, x.dtype
-        gy = gy.contiguous()
-        if gy.dtype != dt:
-            gy = gy.to(dt)
+        gy = K.grad_in(gy, dt)
         code = N.dtype_code(x)
         gx = gw = gb = None
         want_gb = bdt is not None and ctx.needs_input_grad[2]
@@ -156,16 +154,16 @@ class _ConvT3x3S2(torch.autograd.Function):
                 STATS["native_dgrad"] += 1
             if ctx.needs_input_grad[1] or want_gb:
                 need = int(N.lib.ssdk_convt_train_wgrad_workspace_bytes(n, cin, cout, h, wd))
-                ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+                ws, wp = K.workspace(dev, need)
                 gw32 = torch.empty((cin, cout, 3, 3), device=dev, dtype=torch.float32)
                 gb32 = torch.empty((cout,), device=dev, dtype=torch.float32) if want_gb else None
                 N.check(N.lib.ssdk_convt_train_wgrad(x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), None if gb32 is None else gb32.data_ptr(),
-                                                     (ws.data_ptr() + 15) & ~15, need, n, cin, cout, h, wd, code, sp), "convt_train_wgrad")
+                                                     wp, need, n, cin, cout, h, wd, code, sp), "convt_train_wgrad")
                 STATS["native_wgrad"] += 1
                 if ctx.needs_input_grad[1]:
-                    gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
+                    gw = K.weight_grad_out(gw32, wdt)
                 if want_gb:
-                    gb = gb32 if bdt == torch.float32 else gb32.to(bdt)
+                    gb = K.weight_grad_out(gb32, bdt)
         return gx, gw, gb, (gy if ctx.needs_input_grad[3] else None)
 
 
@@ -174,7 +172,7 @@ def _describe(t):
 
 
 def _kernel_tensor(t):
-    return torch.is_tensor(t) and t.is_cuda and t.dim() == 4 and t.dtype in _HALF and t.is_contiguous()
+    return torch.is_tensor(t) and t.is_cuda and t.dim() == 4 and t.dtype in K.HALF and t.is_contiguous()
 
 
 def _skip_fits(x, skip, cout):
@@ -224,7 +222,7 @@ class ShelfConvT(nn.ConvTranspose2d):
             xk = x.to(torch.get_autocast_dtype("cuda"))
             if sk is not None and torch.is_tensor(sk):
                 sk = sk.to(xk.dtype)
-        if xk.dtype not in _HALF or (w.dtype != torch.float32 and w.dtype != xk.dtype) or w.device != xk.device:
+        if xk.dtype not in K.HALF or (w.dtype != torch.float32 and w.dtype != xk.dtype) or w.device != xk.device:
             return self._module_path(x, output_size, skip)
         if sk is not None and not (_kernel_tensor(sk) and _skip_fits(xk, sk, self.out_channels)):
             return self._module_path(x, output_size, skip)

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from ssds import _native as N
+from ssds.modeling.layers import kernel_conv as K
 
 MIN_CIN, MAX_CIN, MIN_COUT, MAX_COUT = 16, 4096, 4, 4096  # csrc/ssdk_conv3train.hip c3_shape_ok
 STATS = {"swapped": 0, "native_forward": 0, "native_dgrad": 0, "native_wgrad": 0}
@@ -87,82 +88,28 @@ def prepare_images(weight, dtype, want_dgrad=True):
     return fwd, dg
 
 
-class _DenseConv3x3(torch.autograd.Function):
-    """x [N, Cin, H, W] 16 bit, contiguous; weight [Cout, Cin, 3, 3] fp32 (the master parameter under autocast: the weight
-    gradient comes back in fp32) or in x's dtype; bias or None (added in fp32 by the forward kernel; its gradient is a torch sum)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride):
-        n, cin, h, wd = (int(v) for v in x.shape)
-        cout = int(weight.shape[0])
-        dev, dt = x.device, x.dtype
-        ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
-        code = N.dtype_code(x)
-        x = x.detach()
-        fwd, dg = prepare_images(weight, dt, want_dgrad=ctx.needs_input_grad[0])
-        b32 = None if bias is None else bias.detach().float().contiguous()
-        y = torch.empty((n, cout, ho, wo), device=dev, dtype=dt)
-        with torch.cuda.device(dev):
-            N.check(N.lib.ssdk_conv3x3_train_forward(x.data_ptr(), fwd.data_ptr(), None if b32 is None else b32.data_ptr(), y.data_ptr(),
-                                                     n, cin, cout, h, wd, stride, code, N.stream_ptr(dev)), "conv3x3_train_forward")
-        STATS["native_forward"] += 1
-        ctx.save_for_backward(x, dg)
-        ctx.meta = (weight.dtype, None if bias is None else bias.dtype, stride, cout)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, dg = ctx.saved_tensors
-        wdt, bdt, stride, cout = ctx.meta
-        n, cin, h, wd = (int(v) for v in x.shape)
-        dev, dt = x.device, x.dtype
-        gy = gy.contiguous()
-        if gy.dtype != dt:
-            gy = gy.to(dt)
-        code = N.dtype_code(x)
-        gx = gw = gb = None
-        with torch.cuda.device(dev):
-            sp = N.stream_ptr(dev)
-            if ctx.needs_input_grad[0]:
-                gx = torch.empty_like(x)
-                N.check(N.lib.ssdk_conv3x3_train_dgrad(gy.data_ptr(), dg.data_ptr(), gx.data_ptr(), n, cin, cout, h, wd, stride, code, sp),
-                        "conv3x3_train_dgrad")
-                STATS["native_dgrad"] += 1
-            if ctx.needs_input_grad[1]:
-                need = int(N.lib.ssdk_conv3x3_train_wgrad_workspace_bytes(n, cin, cout, h, wd, stride))
-                ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
-                gw32 = torch.empty((cout, cin, 3, 3), device=dev, dtype=torch.float32)
-                N.check(N.lib.ssdk_conv3x3_train_wgrad(x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), (ws.data_ptr() + 15) & ~15, need,
-                                                       n, cin, cout, h, wd, stride, code, sp), "conv3x3_train_wgrad")
-                STATS["native_wgrad"] += 1
-                gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
-        if bdt is not None and ctx.needs_input_grad[2]:
-            gb = gy.sum((0, 2, 3), dtype=torch.float32).to(bdt)
-        return gx, gw, gb, None
+# (bias added in fp32 by the forward kernel; its gradient is a torch sum)
+FAMILY = K.ImageFamily(name="conv3x3_train", stats=STATS, kernel_bias=True,
+                       prepare=lambda weight, groups, dtype, want_dgrad: prepare_images(weight, dtype, want_dgrad),
+                       dims=lambda n, cin, cout, h, w, groups, stride: (n, cin, cout, h, w, stride),
+                       forward=N.lib.ssdk_conv3x3_train_forward, dgrad=N.lib.ssdk_conv3x3_train_dgrad,
+                       wgrad=N.lib.ssdk_conv3x3_train_wgrad, wgrad_workspace_bytes=N.lib.ssdk_conv3x3_train_wgrad_workspace_bytes)
 
 
 def dense_conv3x3(x, weight, bias=None, stride=1):
     """The native path, called explicitly: x 16-bit contiguous NCHW on a HIP device; differentiable."""
-    return _DenseConv3x3.apply(x, weight, bias, stride)
+    return K.ImageConv3x3.apply(x, weight, bias, stride, 1, FAMILY)
 
 
-class DenseConv3x3(nn.Conv2d):
+class DenseConv3x3(K.KernelConv2d):
     """``nn.Conv2d(Cin, Cout, 3, stride 1 | 2, pad 1)`` whose 16-bit HIP-device forward / backward run on
     csrc/ssdk_conv3train.hip (same parameters, ``state_dict`` keys and initialisation); everything else is ``nn.Conv2d.forward``."""
 
-    def _native(self, x):
-        return x.is_cuda and x.dim() == 4 and x.is_contiguous() and int(x.shape[1]) == self.in_channels and supported(self)
+    matches = staticmethod(supported)
+    half_weight = True
 
-    def forward(self, x):
-        if not self._native(x):
-            return super(DenseConv3x3, self).forward(x)
-        w = self.weight
-        if torch.is_autocast_enabled():
-            x = x.to(torch.get_autocast_dtype("cuda"))
-        if x.dtype not in (torch.bfloat16, torch.float16) or (w.dtype != torch.float32 and w.dtype != x.dtype):
-            return super(DenseConv3x3, self).forward(x)
-        with torch.autocast("cuda", enabled=False):
-            return _DenseConv3x3.apply(x, w, self.bias, self.stride[0])
+    def _run(self, x, w):
+        return K.ImageConv3x3.apply(x, w, self.bias, self.stride[0], 1, FAMILY)
 
 
 # what an unset SSDK_DENSE3_TRAIN means on SSDFPN / SSDBiFPN models (train_routing.PASSES picks between this and YOLO_DEFAULT by the
@@ -180,8 +127,5 @@ YOLO_DEFAULT = "0"  # (SSDShelf models too: never timed there, slower on the oth
 def use_native_dense3x3(model):
     """Switch every dense 3x3 ``nn.Conv2d`` of ``model`` that ``supported`` accepts to the kernel-backed subclass (in place; no
     new parameters, same ``state_dict``).  -> model; STATS["swapped"] counts the layers."""
-    for m in model.modules():
-        if type(m) is nn.Conv2d and supported(m):
-            m.__class__ = DenseConv3x3
-            STATS["swapped"] += 1
+    STATS["swapped"] += K.swap_layers(model, DenseConv3x3)
     return model

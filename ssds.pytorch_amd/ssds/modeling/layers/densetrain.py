@@ -35,6 +35,7 @@ import torch.nn as nn
 
 from ssds import _native as N
 from ssds.modeling.layers import denseconv
+from ssds.modeling.layers import kernel_conv as K
 from ssds.modeling.layers import shuffletrain as ST
 from ssds.modeling.layers.batchnorm import _ws as _bn_ws
 from ssds.modeling.nets.densenet import _DenseBlock, _DenseLayer
@@ -42,7 +43,6 @@ from ssds.modeling.nets.densenet import _DenseBlock, _DenseLayer
 GROWTH, CMID = 32, 128  # the widths the path is built and tested for (DenseNet121 / 169 / 201): conv2 is 128 -> 32
 STATS = {"swapped": 0, "native_forward": 0, "forward_layers": 0, "backward_layers": 0, "fallback": 0}
 FALLBACK_REASONS = collections.Counter()  # reason -> count of the forwards that took _DenseBlock.forward
-_HALF = (torch.bfloat16, torch.float16)
 
 
 # ---- summation depths: the longest chain of dependent fp32 additions a term passes through (the bars of tests/test_gpu_dense_train.py)
@@ -81,28 +81,24 @@ def pw_wgrad_sum_depth(b, m, k, hw):
 
 
 # ---- the five entry points on raw pointers (the block function and the tests share them) ---------------------------------------
-def _aligned(t):
-    return (t.data_ptr() + 15) & ~15
-
-
 def place(t, y_ptr, y_stride, sums_ptr, n, c, hw, code, dev):
     """ssdk_dense_train_place: contiguous t [n, c, hw] -> the slice at ``y_ptr``; (sum, sum of squares) -> ``sums_ptr`` [c, 2]."""
     need = int(N.lib.ssdk_dense_train_place_workspace_bytes(n, c, hw))
-    ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
-    N.check(N.lib.ssdk_dense_train_place(t.data_ptr(), y_ptr, y_stride, sums_ptr, _aligned(ws), need, n, c, hw, code, N.stream_ptr(dev)),
+    ws, wp = K.workspace(dev, need)
+    N.check(N.lib.ssdk_dense_train_place(t.data_ptr(), y_ptr, y_stride, sums_ptr, wp, need, n, c, hw, code, N.stream_ptr(dev)),
             "dense_train_place")
 
 
 def pw_forward(x_ptr, x_stride, coef, a, m, b, k, cm, hw, code, dev, want_sums=True):
     """ssdk_dense_train_pw_forward: m [b, cm, hw] = a op(x); -> sums [cm, 2] or None."""
-    sums = ws = None
+    sums = ws = wp = None
     need = 0
     if want_sums:
         need = int(N.lib.ssdk_pws_stats_workspace_bytes(b, k, cm, hw))
-        ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+        ws, wp = K.workspace(dev, need)
         sums = torch.empty((cm, 2), device=dev, dtype=torch.float32)
     N.check(N.lib.ssdk_dense_train_pw_forward(x_ptr, x_stride, coef.data_ptr(), a.data_ptr(), int(a.shape[1]), m.data_ptr(),
-                                              None if sums is None else sums.data_ptr(), None if ws is None else _aligned(ws), need,
+                                              None if sums is None else sums.data_ptr(), wp, need,
                                               b, k, cm, hw, code, N.stream_ptr(dev)), "dense_train_pw_forward")
     return sums
 
@@ -110,9 +106,9 @@ def pw_forward(x_ptr, x_stride, coef, a, m, b, k, cm, hw, code, dev, want_sums=T
 def pw_wgrad(dm, x_ptr, x_stride, coef, b, cm, k, hw, code, dev):
     """ssdk_dense_train_pw_wgrad -> dW [cm, k, 1, 1] fp32."""
     need = int(N.lib.ssdk_pws_wgrad_workspace_bytes(b, cm, k, hw))
-    ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+    ws, wp = K.workspace(dev, need)
     gw = torch.empty((cm, k, 1, 1), device=dev, dtype=torch.float32)
-    N.check(N.lib.ssdk_dense_train_pw_wgrad(dm.data_ptr(), x_ptr, x_stride, coef.data_ptr(), gw.data_ptr(), _aligned(ws), need, b, cm, k,
+    N.check(N.lib.ssdk_dense_train_pw_wgrad(dm.data_ptr(), x_ptr, x_stride, coef.data_ptr(), gw.data_ptr(), wp, need, b, cm, k,
                                             hw, code, N.stream_ptr(dev)), "dense_train_pw_wgrad")
     return gw
 
@@ -120,10 +116,10 @@ def pw_wgrad(dm, x_ptr, x_stride, coef, b, cm, k, hw, code, dev):
 def bn1_reduce(s_ptr, x_ptr, x_stride, coef, mean, invstd, n, k, hw, code, dev):
     """ssdk_dense_train_bn1_reduce -> red [k, 2] fp32 = (d bias, d weight) of norm1."""
     need = int(N.lib.ssdk_dense_train_bn1_workspace_bytes(n, k, hw))
-    ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+    ws, wp = K.workspace(dev, need)
     red = torch.empty((k, 2), device=dev, dtype=torch.float32)
     N.check(N.lib.ssdk_dense_train_bn1_reduce(s_ptr, x_ptr, x_stride, coef.data_ptr(), mean.data_ptr(), invstd.data_ptr(), red.data_ptr(),
-                                              _aligned(ws), need, n, k, hw, code, N.stream_ptr(dev)), "dense_train_bn1_reduce")
+                                              wp, need, n, k, hw, code, N.stream_ptr(dev)), "dense_train_bn1_reduce")
     return red
 
 
@@ -193,9 +189,9 @@ def layer_backward(F, G, scratch, k, saved, params, need, flows):
             "conv3x3_train_dgrad")
     if need[5]:
         nb = int(N.lib.ssdk_conv3x3_train_wgrad_workspace_bytes(n, CMID, GROWTH, h, w, 1))
-        ws = torch.empty(nb + 16, dtype=torch.uint8, device=dev)
+        ws, wp = K.workspace(dev, nb)
         grads[5] = torch.empty((GROWTH, CMID, 3, 3), device=dev, dtype=torch.float32)
-        N.check(N.lib.ssdk_conv3x3_train_wgrad(r2.data_ptr(), gnew.data_ptr(), grads[5].data_ptr(), _aligned(ws), nb, n, CMID, GROWTH, h, w, 1,
+        N.check(N.lib.ssdk_conv3x3_train_wgrad(r2.data_ptr(), gnew.data_ptr(), grads[5].data_ptr(), wp, nb, n, CMID, GROWTH, h, w, 1,
                                                code, sp), "conv3x3_train_wgrad")
     dm = torch.empty_like(m)
     gg2 = torch.empty(CMID, device=dev, dtype=torch.float32)
@@ -306,7 +302,7 @@ class TrainDenseBlock(_DenseBlock):
         if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.numel() > 0):
             return "not a 4-d tensor on a HIP device"
         dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
-        if dt not in _HALF:
+        if dt not in K.HALF:
             return "fp32 without autocast"
         for l in self.values():
             if l.drop_rate > 0:

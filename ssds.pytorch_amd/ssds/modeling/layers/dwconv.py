@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from ssds import _native as N
+from ssds.modeling.layers import kernel_conv as K
 
 
 def _launch(fn, *args):
@@ -58,18 +59,17 @@ class _DwConv3x3(torch.autograd.Function):
         with torch.cuda.device(x.device):
             need = int(N.lib.ssdk_dwconv_fwd_stats_workspace_bytes(n, c, h, wd, stride, N.dtype_code(x))) if want_sums else 0
             if coef is not None:  # x is the INPUT of a deferred BatchNorm: the kernel stages act(a x + b) (batchnorm._BatchNormDeferred)
-                ws = torch.empty(need + 16, dtype=torch.uint8, device=x.device) if need else None
+                ws, wp = K.workspace(x.device, need) if need else (None, None)
                 if need:
                     sums = torch.empty((c, 2), device=x.device, dtype=torch.float32)
                 N.check(N.lib.ssdk_dwconv_fwd_affine(x.data_ptr(), coef.data_ptr(), int(act), w.data_ptr(), y.data_ptr(),
-                                                     None if sums is None else sums.data_ptr(),
-                                                     None if ws is None else (ws.data_ptr() + 15) & ~15, need, n, c, h, wd, stride,
+                                                     None if sums is None else sums.data_ptr(), wp, need, n, c, h, wd, stride,
                                                      N.dtype_code(x), N.stream_ptr(x.device)), "dwconv_fwd_affine")
             elif need:
-                ws = torch.empty(need + 16, dtype=torch.uint8, device=x.device)
+                ws, wp = K.workspace(x.device, need)
                 sums = torch.empty((c, 2), device=x.device, dtype=torch.float32)
-                N.check(N.lib.ssdk_dwconv_fwd_stats(x.data_ptr(), w.data_ptr(), y.data_ptr(), sums.data_ptr(), (ws.data_ptr() + 15) & ~15,
-                                                    need, n, c, h, wd, stride, N.dtype_code(x), N.stream_ptr(x.device)), "dwconv_fwd_stats")
+                N.check(N.lib.ssdk_dwconv_fwd_stats(x.data_ptr(), w.data_ptr(), y.data_ptr(), sums.data_ptr(), wp, need, n, c, h, wd, stride,
+                                                    N.dtype_code(x), N.stream_ptr(x.device)), "dwconv_fwd_stats")
             else:
                 _launch(N.lib.ssdk_dwconv_fwd, x.data_ptr(), w.data_ptr(), y.data_ptr(), n, c, h, wd, stride, N.dtype_code(x),
                         N.stream_ptr(x.device))
@@ -97,9 +97,7 @@ class _DwConv3x3(torch.autograd.Function):
         stride = ctx.stride
         if gy is None:  # (only the non-differentiable statistics were used)
             return None, None, None, None, None, None
-        gy = gy.contiguous()
-        if gy.dtype != x.dtype:
-            gy = gy.to(x.dtype)
+        gy = K.grad_in(gy, x.dtype)
         n, c, h, wd = (int(v) for v in x.shape)
         gx = gw = None
         dev = x.device
@@ -110,16 +108,16 @@ class _DwConv3x3(torch.autograd.Function):
                         N.dtype_code(x), N.stream_ptr(dev))
             if ctx.needs_input_grad[1]:
                 need = int(N.lib.ssdk_dwconv_bwd_weight_workspace_bytes(n, c, h, wd, stride))
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                ws, wp = K.workspace(dev, need)
                 gw32 = torch.empty((c, 1, 3, 3), device=dev, dtype=torch.float32)
                 if coef is not None:
                     N.check(N.lib.ssdk_dwconv_bwd_weight_affine(x.data_ptr(), coef.data_ptr(), ctx.act, gy.data_ptr(), gw32.data_ptr(),
-                                                                ws.data_ptr(), need, n, c, h, wd, stride, N.dtype_code(x),
+                                                                wp, need, n, c, h, wd, stride, N.dtype_code(x),
                                                                 N.stream_ptr(dev)), "dwconv_bwd_weight_affine")
                 else:
-                    _launch(N.lib.ssdk_dwconv_bwd_weight, x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), ws.data_ptr(), need,
+                    _launch(N.lib.ssdk_dwconv_bwd_weight, x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), wp, need,
                             n, c, h, wd, stride, N.dtype_code(x), N.stream_ptr(dev))
-                gw = gw32.to(ctx.wdt)
+                gw = K.weight_grad_out(gw32, ctx.wdt)
         return gx, gw, None, None, None, None
 
 
@@ -141,29 +139,33 @@ class DepthwiseConv2d(nn.Conv2d):
     _ssdk_bn_follows = False  # set by pointwise.fuse_conv_bn_statistics: the next module is a kernel-backed BatchNorm
     _ssdk_expect_pending = False  # set by a deferred BatchNorm right before its (alias) output reaches this module
 
+    @staticmethod
+    def matches(m):
+        """The layer predicate: depthwise 3x3 / pad 1 / stride 1 | 2 without bias (the gate, and the swap of
+        shuffletrain.use_native_shuffle)."""
+        return (m.kernel_size == (3, 3) and m.padding == (1, 1) and m.dilation == (1, 1) and m.stride in ((1, 1), (2, 2))
+                and m.groups == m.in_channels == m.out_channels and m.bias is None and m.padding_mode == "zeros")
+
     def _native(self, x):
-        return (x.is_cuda and x.dim() == 4 and self.kernel_size == (3, 3) and self.padding == (1, 1)
-                and self.dilation == (1, 1) and self.stride[0] == self.stride[1] and self.stride[0] in (1, 2)
-                and self.groups == self.in_channels == self.out_channels and self.bias is None
-                and self.padding_mode == "zeros")
+        return x.is_cuda and x.dim() == 4 and self.matches(self)
 
     def forward(self, x):
         pending = x.__dict__.pop("_ssdk_pending_bn", None) if hasattr(x, "__dict__") else None
         expect, self._ssdk_expect_pending = self._ssdk_expect_pending, False
         if expect and pending is None:  # (would be silently wrong: the tensor in hand is the BatchNorm's INPUT)
             raise RuntimeError("DepthwiseConv2d: the deferred BatchNorm's coefficients did not arrive with its output")
-        if pending is not None and not (self._native(x) and x.dtype in (torch.bfloat16, torch.float16)):
+        if pending is not None and not (self._native(x) and x.dtype in K.HALF):
             raise RuntimeError("DepthwiseConv2d: a deferred BatchNorm output reached a path that cannot apply it")
         if not self._native(x):
             return super(DepthwiseConv2d, self).forward(x)
         w = self.weight
         if torch.is_autocast_enabled():
             x = x.to(torch.get_autocast_dtype("cuda"))
-            if not (w.dtype == torch.float32 and x.dtype in (torch.bfloat16, torch.float16)):
+            if not (w.dtype == torch.float32 and x.dtype in K.HALF):
                 w = w.to(x.dtype)  # (fp32 master weights go in as they are: _DwConv3x3 casts outside autograd)
         elif w.dtype != x.dtype:
             w = w.to(x.dtype)
-        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        if x.dtype not in (torch.float32,) + K.HALF:
             return super(DepthwiseConv2d, self).forward(x)
         from ssds.modeling.layers import pointwise as _pw
 

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from ssds import _native as N
+from ssds.modeling.layers import kernel_conv as K
 from ssds.modeling.layers.fused_conv import pack_grouped_frag
 
 MAX_WIDTH = 256  # channels per group (csrc/ssdk_gconvtrain.hip gt_shape)
@@ -82,89 +83,31 @@ def prepare_images(weight, groups, dtype, want_dgrad=True):
     return fwd, dg
 
 
-class _GroupedConv3x3(torch.autograd.Function):
-    """x [N, C, H, W] 16 bit, contiguous; weight [C, gw, 3, 3] fp32 (the master parameter under autocast: the weight gradient
-    comes back in fp32) or in x's dtype; bias or None (added and reduced on torch: no registered backbone has one)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride, groups):
-        n, c, h, wd = (int(v) for v in x.shape)
-        dev, dt = x.device, x.dtype
-        ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
-        code = N.dtype_code(x)
-        x = x.detach()
-        fwd, dg = prepare_images(weight, groups, dt, want_dgrad=ctx.needs_input_grad[0])
-        y = torch.empty((n, c, ho, wo), device=dev, dtype=dt)
-        with torch.cuda.device(dev):
-            N.check(N.lib.ssdk_gconv3x3_train_forward(x.data_ptr(), fwd.data_ptr(), y.data_ptr(), n, c, h, wd, groups, stride, code,
-                                                      N.stream_ptr(dev)), "gconv3x3_train_forward")
-        STATS["native_forward"] += 1
-        if bias is not None:
-            y += bias.detach().to(dt).view(1, c, 1, 1)
-        ctx.save_for_backward(x, dg)
-        ctx.meta = (weight.dtype, None if bias is None else bias.dtype, stride, groups)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, dg = ctx.saved_tensors
-        wdt, bdt, stride, groups = ctx.meta
-        n, c, h, wd = (int(v) for v in x.shape)
-        dev, dt = x.device, x.dtype
-        gy = gy.contiguous()
-        if gy.dtype != dt:
-            gy = gy.to(dt)
-        code = N.dtype_code(x)
-        gx = gw = gb = None
-        with torch.cuda.device(dev):
-            sp = N.stream_ptr(dev)
-            if ctx.needs_input_grad[0]:
-                gx = torch.empty_like(x)
-                N.check(N.lib.ssdk_gconv3x3_train_dgrad(gy.data_ptr(), dg.data_ptr(), gx.data_ptr(), n, c, h, wd, groups, stride, code, sp),
-                        "gconv3x3_train_dgrad")
-                STATS["native_dgrad"] += 1
-            if ctx.needs_input_grad[1]:
-                need = int(N.lib.ssdk_gconv3x3_train_wgrad_workspace_bytes(n, c, h, wd, groups, stride))
-                ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
-                gw32 = torch.empty((c, c // groups, 3, 3), device=dev, dtype=torch.float32)
-                N.check(N.lib.ssdk_gconv3x3_train_wgrad(x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), (ws.data_ptr() + 15) & ~15, need,
-                                                        n, c, h, wd, groups, stride, code, sp), "gconv3x3_train_wgrad")
-                STATS["native_wgrad"] += 1
-                gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
-        if bdt is not None and ctx.needs_input_grad[2]:
-            gb = gy.sum((0, 2, 3), dtype=torch.float32).to(bdt)
-        return gx, gw, gb, None, None
+# (a bias is added and reduced on torch: no registered backbone has one)
+FAMILY = K.ImageFamily(name="gconv3x3_train", stats=STATS, kernel_bias=False, prepare=prepare_images,
+                       dims=lambda n, cin, cout, h, w, groups, stride: (n, cin, h, w, groups, stride),
+                       forward=N.lib.ssdk_gconv3x3_train_forward, dgrad=N.lib.ssdk_gconv3x3_train_dgrad,
+                       wgrad=N.lib.ssdk_gconv3x3_train_wgrad, wgrad_workspace_bytes=N.lib.ssdk_gconv3x3_train_wgrad_workspace_bytes)
 
 
 def grouped_conv3x3(x, weight, bias=None, stride=1, groups=1):
     """The native path, called explicitly: x 16-bit contiguous NCHW on a HIP device; differentiable."""
-    return _GroupedConv3x3.apply(x, weight, bias, stride, groups)
+    return K.ImageConv3x3.apply(x, weight, bias, stride, groups, FAMILY)
 
 
-class GroupedConv3x3(nn.Conv2d):
+class GroupedConv3x3(K.KernelConv2d):
     """``nn.Conv2d(C, C, 3, stride 1 | 2, pad 1, groups)`` whose 16-bit HIP-device forward / backward run on
     csrc/ssdk_gconvtrain.hip (same parameters, ``state_dict`` keys and initialisation); everything else is ``nn.Conv2d.forward``."""
 
-    def _native(self, x):
-        return x.is_cuda and x.dim() == 4 and x.is_contiguous() and int(x.shape[1]) == self.in_channels and supported(self)
+    matches = staticmethod(supported)
+    half_weight = True
 
-    def forward(self, x):
-        if not self._native(x):
-            return super(GroupedConv3x3, self).forward(x)
-        w = self.weight
-        if torch.is_autocast_enabled():
-            x = x.to(torch.get_autocast_dtype("cuda"))
-        if x.dtype not in (torch.bfloat16, torch.float16) or (w.dtype != torch.float32 and w.dtype != x.dtype):
-            return super(GroupedConv3x3, self).forward(x)
-        with torch.autocast("cuda", enabled=False):
-            return _GroupedConv3x3.apply(x, w, self.bias, self.stride[0], self.groups)
+    def _run(self, x, w):
+        return K.ImageConv3x3.apply(x, w, self.bias, self.stride[0], self.groups, FAMILY)
 
 
 def use_native_gconv(model):
     """Switch every grouped 3x3 ``nn.Conv2d`` of ``model`` that ``supported`` accepts to the kernel-backed subclass (in place; no
     new parameters, same ``state_dict``).  -> model; STATS["swapped"] counts the layers."""
-    for m in model.modules():
-        if type(m) is nn.Conv2d and supported(m):
-            m.__class__ = GroupedConv3x3
-            STATS["swapped"] += 1
+    STATS["swapped"] += K.swap_layers(model, GroupedConv3x3)
     return model

@@ -14,6 +14,7 @@ import os
 import torch
 
 from ssds import _native as N
+from ssds.modeling.layers import kernel_conv as K
 from ssds.modeling.layers import fused_conv as FC
 
 
@@ -145,13 +146,13 @@ def _weight_gradients(x, pairs, has_bias):
         kp = int(col.shape[1])
         gn, ghw = (1, n * hw) if fold else (n, hw)
         for g, wt in pairs:
-            g = g.to(dt).contiguous()
+            g = K.grad_in(g, dt)
             cout = int(wt.shape[0])
             g2 = PW._fold(g.view(n, cout, hw)) if fold else g
             need = int(N.lib.ssdk_pw_wgrad_workspace_bytes(gn, cout, kp, ghw))
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws, wp = K.workspace(dev, need)
             gw32 = torch.empty((cout, kp), device=dev, dtype=torch.float32)
-            N.check(N.lib.ssdk_pw_wgrad(g2.data_ptr(), col.data_ptr(), gw32.data_ptr(), ws.data_ptr(), need, gn, cout, kp, ghw, N.dtype_code(x), sp),
+            N.check(N.lib.ssdk_pw_wgrad(g2.data_ptr(), col.data_ptr(), gw32.data_ptr(), wp, need, gn, cout, kp, ghw, N.dtype_code(x), sp),
                     "pw_wgrad (head pair)")
             gw = gw32[:, : cin * 9].reshape(cout, cin, 3, 3)
             gb = g.sum((0, 2, 3), dtype=torch.float32) if has_bias else None

@@ -6,11 +6,11 @@ their classes, parameters and ``state_dict`` keys.  DESIGN.md 4.6b."""
 import torch
 
 from ssds import _native as N
+from ssds.modeling.layers import kernel_conv as K
 from ssds.modeling.nets.efficientnet import MBConvBlock
 
 STATS = {"swapped": 0, "native_forward": 0, "fallback": 0}
 MAX_C, MAX_R = 4096, 1024  # csrc/ssdk_mbconvtrain.hip kSeMaxC / kSeMaxR (LDS of the gate kernels)
-_HALF = (torch.bfloat16, torch.float16)
 
 
 # ---- summation depths: the longest chain of dependent fp32 additions a term passes through (the bars of tests/mbconvjudge.py) ----
@@ -95,9 +95,7 @@ class _DwConv5x5(torch.autograd.Function):
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
         stride, dev = ctx.stride, x.device
-        gy = gy.contiguous()
-        if gy.dtype != x.dtype:
-            gy = gy.to(x.dtype)
+        gy = K.grad_in(gy, x.dtype)
         n, c, h, wd = (int(v) for v in x.shape)
         gx = gw = None
         with torch.cuda.device(dev):
@@ -107,11 +105,11 @@ class _DwConv5x5(torch.autograd.Function):
                                                     N.stream_ptr(dev)), "dwconv5_bwd_data")
             if ctx.needs_input_grad[1]:
                 need = int(N.lib.ssdk_dwconv5_bwd_weight_workspace_bytes(n, c, h, wd, stride))
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                ws, wp = K.workspace(dev, need)
                 gw32 = torch.empty((c, 1, 5, 5), device=dev, dtype=torch.float32)
-                N.check(N.lib.ssdk_dwconv5_bwd_weight(x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), ws.data_ptr(), need, n, c, h, wd,
+                N.check(N.lib.ssdk_dwconv5_bwd_weight(x.data_ptr(), gy.data_ptr(), gw32.data_ptr(), wp, need, n, c, h, wd,
                                                       stride, N.dtype_code(x), N.stream_ptr(dev)), "dwconv5_bwd_weight")
-                gw = gw32.to(ctx.wdt)
+                gw = K.weight_grad_out(gw32, ctx.wdt)
         return gx, gw, None
 
 
@@ -123,7 +121,7 @@ def dwconv5x5(x, weight, stride):
     if x.dim() != 4 or tuple(weight.shape) != (int(x.shape[1]), 1, 5, 5) or stride not in (1, 2):
         raise N.SsdkError("dwconv5x5: x [N, C, H, W], weight [C, 1, 5, 5], stride 1 | 2 expected, got {}, {}, {}".format(
             tuple(x.shape), tuple(weight.shape), stride))
-    if x.dtype not in _HALF or weight.dtype not in (torch.float32, x.dtype):
+    if x.dtype not in K.HALF or weight.dtype not in (torch.float32, x.dtype):
         raise N.SsdkError("dwconv5x5: a 16-bit x and an fp32 / same-dtype weight expected, got {} and {}".format(x.dtype, weight.dtype))
     with torch.autocast("cuda", enabled=False):
         return _DwConv5x5.apply(x, weight, int(stride))
@@ -193,7 +191,7 @@ def silu_squeeze_excite(u, w1, b1, w2, b2):
         raise N.SsdkError("silu_squeeze_excite: u [N, C, H, W], w1 [Cr, C(, 1, 1)], b1 [Cr], w2 [C, Cr(, 1, 1)], b2 [C] with C <= {}, "
                           "Cr <= {} expected, got {}, {}, {}, {}, {}".format(MAX_C, MAX_R, tuple(u.shape), tuple(w1.shape),
                                                                              tuple(b1.shape), tuple(w2.shape), tuple(b2.shape)))
-    if u.dtype not in _HALF or any(t.dtype != torch.float32 for t in (w1, b1, w2, b2)):
+    if u.dtype not in K.HALF or any(t.dtype != torch.float32 for t in (w1, b1, w2, b2)):
         raise N.SsdkError("silu_squeeze_excite: a 16-bit u and fp32 parameters expected")
     with torch.autocast("cuda", enabled=False):
         return _SiluSqueezeExcite.apply(u, w1, b1, w2, b2)
@@ -224,7 +222,7 @@ class TrainMBConvBlock(MBConvBlock):
         if not (self.training and torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
             return None
         dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
-        if dt not in _HALF:
+        if dt not in K.HALF:
             return None
         _, dw, se, _, _ = self.parts()
         if any(p.dtype != torch.float32 for p in (se.se[1].weight, se.se[1].bias, se.se[3].weight, se.se[3].bias)):

@@ -21,6 +21,8 @@ import torch
 import torch.nn as nn
 
 from ssds import _native as N
+from ssds.modeling.layers import kernel_conv as K
+from ssds.modeling.layers.stemconv import StemConv3x3s2, use_native_stem  # noqa: F401 -- (they moved next to the 7x7 stem)
 
 
 class _Pointwise(torch.autograd.Function):
@@ -64,7 +66,7 @@ class _Pointwise(torch.autograd.Function):
 def _native_ok(x, cin, cout=0, any_width=False):
     """``any_width`` (a layer marked by shuffletrain.use_native_shuffle): input widths that are no multiple of 8 go to the
     ssdk_pws_* kernels of csrc/ssdk_shuffletrain.hip (at least 8 channels either side)."""
-    return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16)
+    return (x.is_cuda and x.dtype in K.HALF
             and (cin % 8 == 0 or (any_width and cin >= 8 and cout >= 8))
             and os.environ.get("SSDK_PW_NATIVE", "1") != "0")
 
@@ -122,10 +124,10 @@ class _PointwiseNative(torch.autograd.Function):
             sums = None
             if want_sums:
                 need = int(N.lib.ssdk_pw_stats_workspace_bytes(b, cin, cout, hw))
-                ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+                ws, wp = K.workspace(dev, need)
                 sums = torch.empty((cout, 2), device=dev, dtype=torch.float32)
                 N.check(N.lib.ssdk_pw_forward_stats(x.data_ptr(), w16.data_ptr(), None if b32 is None else b32.data_ptr(), y.data_ptr(),
-                                                    sums.data_ptr(), (ws.data_ptr() + 15) & ~15, need, b, cin, cout, hw, code, sp),
+                                                    sums.data_ptr(), wp, need, b, cin, cout, hw, code, sp),
                         "pw_forward_stats")
             else:
                 N.check(N.lib.ssdk_pw_forward(x.data_ptr(), w16.data_ptr(), None if b32 is None else b32.data_ptr(), y.data_ptr(),
@@ -147,9 +149,7 @@ class _PointwiseNative(torch.autograd.Function):
         cout, hw, dev = ctx.cout, h * wd, x.device
         if gy is None:  # (only the non-differentiable statistics were used)
             return None, None, None, None, None
-        gy = gy.contiguous()
-        if gy.dtype != x.dtype:
-            gy = gy.to(x.dtype)
+        gy = K.grad_in(gy, x.dtype)
         code = N.dtype_code(x)
         gx = gw = gb = None
         with torch.cuda.device(dev):
@@ -169,17 +169,15 @@ class _PointwiseNative(torch.autograd.Function):
             if ctx.needs_input_grad[1] and ctx.padded and cin % 8 != 0:
                 from ssds.modeling.layers import shuffletrain as ST
 
-                gw32 = ST.pws_wgrad(gy, x.data_ptr(), cin * hw, b, cout, cin, hw, code, dev)
-                gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
+                gw = K.weight_grad_out(ST.pws_wgrad(gy, x.data_ptr(), cin * hw, b, cout, cin, hw, code, dev), wdt)
             elif ctx.needs_input_grad[1]:
                 need = int(N.lib.ssdk_pw_wgrad_workspace_bytes(b, cout, cin, hw))
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                ws, wp = K.workspace(dev, need)
                 gw32 = torch.empty((cout, cin, 1, 1), device=dev, dtype=torch.float32)
-                N.check(N.lib.ssdk_pw_wgrad(gy.data_ptr(), x.data_ptr(), gw32.data_ptr(), ws.data_ptr(), need, b, cout, cin, hw, code,
-                                            sp), "pw_wgrad")
-                gw = gw32 if wdt == torch.float32 else gw32.to(wdt)
+                N.check(N.lib.ssdk_pw_wgrad(gy.data_ptr(), x.data_ptr(), gw32.data_ptr(), wp, need, b, cout, cin, hw, code, sp), "pw_wgrad")
+                gw = K.weight_grad_out(gw32, wdt)
         if bdt is not None and ctx.needs_input_grad[2]:
-            gb = gy.sum((0, 2, 3), dtype=torch.float32).to(bdt)
+            gb = K.bias_grad(gy, bdt)
         return gx, gw, gb, None, None
 
 
@@ -206,10 +204,15 @@ class PointwiseConv2d(nn.Conv2d):
     _ssdk_bn_follows = False  # set by fuse_conv_bn_statistics: the next module is a kernel-backed BatchNorm in training mode
     _ssdk_any_width = False  # set by shuffletrain.use_native_shuffle: widths that are no multiple of 8 take the ssdk_pws_* kernels
 
+    @staticmethod
+    def matches(m):
+        """What ``use_pointwise_gemm`` takes: the dense 1x1 / stride 1 / pad 0 layers, whatever their ``padding_mode`` (there is
+        nothing to pad)."""
+        return m.kernel_size == (1, 1) and m.stride == (1, 1) and m.padding == (0, 0) and m.groups == 1 and m.dilation == (1, 1)
+
     def _native(self, x):
-        return (x.is_cuda and x.dim() == 4 and self.kernel_size == (1, 1) and self.stride == (1, 1)
-                and self.padding == (0, 0) and self.dilation == (1, 1) and self.groups == 1
-                and self.padding_mode == "zeros" and x.is_contiguous())
+        # (narrower than ``matches``, at run time only: a layer with another padding_mode is taken and left on nn.Conv2d.forward)
+        return x.is_cuda and x.dim() == 4 and self.matches(self) and self.padding_mode == "zeros" and x.is_contiguous()
 
     def forward(self, x):
         if not self._native(x):
@@ -256,10 +259,7 @@ def fuse_conv_bn_statistics(model):
 def use_pointwise_gemm(model):
     """Switch every dense 1x1 / stride-1 ``nn.Conv2d`` of ``model`` to the GEMM-backed subclass (in place; no new
     parameters, same ``state_dict``)."""
-    for m in model.modules():
-        if (type(m) is nn.Conv2d and m.kernel_size == (1, 1) and m.stride == (1, 1) and m.padding == (0, 0)
-                and m.groups == 1 and m.dilation == (1, 1)):
-            m.__class__ = PointwiseConv2d
+    K.swap_layers(model, PointwiseConv2d)
     return model
 
 
@@ -346,9 +346,7 @@ class _Conv3x3Native(torch.autograd.Function):
         wdt, bdt, (b, cin, h, wd), stride, fold = ctx.meta
         kp, cout = (int(v) for v in wt16.shape)
         gb, ghw, dev, dt = int(col.shape[0]), int(col.shape[2]), col.device, col.dtype
-        gy = gy.contiguous()
-        if gy.dtype != dt:
-            gy = gy.to(dt)
+        gy = K.grad_in(gy, dt)
         g3 = gy.view(b, cout, -1)
         gf = _fold(g3) if fold else g3  # [gb, cout, ghw]
         code = N.dtype_code(col)
@@ -367,126 +365,37 @@ class _Conv3x3Native(torch.autograd.Function):
                 N.check(fn(dcol.data_ptr(), gx.data_ptr(), b, cin, h, wd, stride, code, sp), "col2im3x3")
             if ctx.needs_input_grad[1]:
                 need = int(N.lib.ssdk_pw_wgrad_workspace_bytes(gb, cout, kp, ghw))
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                ws, wp = K.workspace(dev, need)
                 gw32 = torch.empty((cout, kp), device=dev, dtype=torch.float32)
-                N.check(N.lib.ssdk_pw_wgrad(gf.data_ptr(), col.data_ptr(), gw32.data_ptr(), ws.data_ptr(), need, gb, cout, kp, ghw, code, sp),
+                N.check(N.lib.ssdk_pw_wgrad(gf.data_ptr(), col.data_ptr(), gw32.data_ptr(), wp, need, gb, cout, kp, ghw, code, sp),
                         "pw_wgrad (3x3)")
-                gw = gw32[:, : cin * 9].reshape(cout, cin, 3, 3)
-                gw = gw if wdt == torch.float32 else gw.to(wdt)
+                gw = K.weight_grad_out(gw32[:, : cin * 9].reshape(cout, cin, 3, 3), wdt)
         if bdt is not None and ctx.needs_input_grad[2]:
-            gbias = gy.sum((0, 2, 3), dtype=torch.float32).to(bdt)
+            gbias = K.bias_grad(gy, bdt)
         return gx, gw, gbias, None
 
 
-class NativeConv3x3(nn.Conv2d):
+class NativeConv3x3(K.KernelConv2d):
     """``nn.Conv2d(k = 3, pad = 1, stride 1 | 2)`` whose 16-bit HIP-device forward / backward run on the ssdk kernels (same
     parameters, ``state_dict`` keys and initialisation); everything else is ``nn.Conv2d.forward``."""
 
-    def _native(self, x):
-        return (x.is_cuda and x.dim() == 4 and self.kernel_size == (3, 3) and self.padding == (1, 1) and self.dilation == (1, 1)
-                and self.stride in ((1, 1), (2, 2)) and self.groups == 1 and self.padding_mode == "zeros" and x.is_contiguous()
-                and os.environ.get("SSDK_CONV3_NATIVE", "1") != "0")
+    half_weight = True
+    checks_width = False
 
-    def forward(self, x):
-        if not self._native(x):
-            return super(NativeConv3x3, self).forward(x)
-        w, bias = self.weight, self.bias
-        if torch.is_autocast_enabled():
-            x = x.to(torch.get_autocast_dtype("cuda"))
-        if x.dtype not in (torch.bfloat16, torch.float16) or (w.dtype != torch.float32 and w.dtype != x.dtype):
-            return super(NativeConv3x3, self).forward(x)
-        with torch.autocast("cuda", enabled=False):
-            return _Conv3x3Native.apply(x, w, bias, self.stride[0])
+    @staticmethod
+    def matches(m):
+        return (m.kernel_size == (3, 3) and m.padding == (1, 1) and m.dilation == (1, 1) and m.stride in ((1, 1), (2, 2))
+                and m.groups == 1 and m.padding_mode == "zeros")
+
+    def runs(self):
+        return os.environ.get("SSDK_CONV3_NATIVE", "1") != "0"
+
+    def _run(self, x, w):
+        return _Conv3x3Native.apply(x, w, self.bias, self.stride[0])
 
 
 def use_native_conv3x3(model, min_in_channels=0):
     """Switch every dense 3x3 / pad 1 / stride 1 | 2 ``nn.Conv2d`` of ``model`` with at least ``min_in_channels`` input channels
     to the kernel-backed subclass (in place)."""
-    for m in model.modules():
-        if (type(m) is nn.Conv2d and m.kernel_size == (3, 3) and m.padding == (1, 1) and m.stride in ((1, 1), (2, 2))
-                and m.groups == 1 and m.dilation == (1, 1) and m.padding_mode == "zeros" and m.in_channels >= min_in_channels):
-            m.__class__ = NativeConv3x3
+    K.swap_layers(model, NativeConv3x3, also=lambda m: m.in_channels >= min_in_channels)
     return model
-
-
-# ---- the network's first convolution (3x3 / stride 2 / pad 1 on the image) on its own kernels (csrc/ssdk_stemtrain.hip) ------------
-class _StemConv3x3s2(torch.autograd.Function):
-    """x [N, Cin <= 3, H, W] 16 bit (contiguous), w [Cout <= 32, Cin, 3, 3] fp32 master parameter -> y [N, Cout, Ho, Wo] 16 bit.
-    Backward: the weight gradient (fp32, matrix cores over pixels, fixed-order partial sums); the image's gradient, if anybody
-    asks for it, comes from the framework's convolution backward."""
-
-    @staticmethod
-    def forward(ctx, x, w):
-        n, cin, h, wd = (int(v) for v in x.shape)
-        cout, dev = int(w.shape[0]), x.device
-        ho, wo = (h - 1) // 2 + 1, (wd - 1) // 2 + 1
-        x = x.detach()
-        y = torch.empty((n, cout, ho, wo), device=dev, dtype=x.dtype)
-        with torch.cuda.device(dev):
-            N.check(N.lib.ssdk_stem3x3s2_fwd(x.data_ptr(), w.detach().contiguous().data_ptr(), y.data_ptr(), n, cin, h, wd, cout,
-                                             N.dtype_code(x), N.stream_ptr(dev)), "stem3x3s2_fwd")
-        ctx.save_for_backward(x, w)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        n, cin, h, wd = (int(v) for v in x.shape)
-        cout, dev = int(w.shape[0]), x.device
-        gy = gy.contiguous()
-        if gy.dtype != x.dtype:
-            gy = gy.to(x.dtype)
-        gx = gw = None
-        if ctx.needs_input_grad[1] and wd % 16 != 0:
-            # rows that are not whole 16-byte groups (the 300 px configuration): the kernel's element-wise operand path is slower
-            # than the library's weight gradient (tools/run/r06_s43.sh) -- only the forward is ours there
-            gw = torch.ops.aten.convolution_backward(gy, x, w.to(x.dtype), None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1,
-                                                     [False, True, False])[1].to(w.dtype)
-        elif ctx.needs_input_grad[1]:
-            need = int(N.lib.ssdk_stem3x3s2_wgrad_workspace_bytes(n, h))
-            ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
-            wp = (ws.data_ptr() + 15) & ~15
-            gw = torch.empty((cout, cin, 3, 3), device=dev, dtype=torch.float32)
-            with torch.cuda.device(dev):
-                N.check(N.lib.ssdk_stem3x3s2_wgrad(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), wp, need, n, cin, h, wd, cout,
-                                                   N.dtype_code(x), N.stream_ptr(dev)), "stem3x3s2_wgrad")
-            gw = gw if w.dtype == torch.float32 else gw.to(w.dtype)
-        if ctx.needs_input_grad[0]:
-            gx = torch.ops.aten.convolution_backward(gy, x, w.to(x.dtype), None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1,
-                                                     [True, False, False])[0]
-        return gx, gw
-
-
-class StemConv3x3s2(nn.Conv2d):
-    """``nn.Conv2d(Cin <= 3, Cout <= 32, k = 3, stride 2, pad 1, bias = False)`` -- the first layer of the MobileNet backbones --
-    whose 16-bit HIP-device forward / weight gradient run on ``csrc/ssdk_stemtrain.hip`` (same parameter, ``state_dict`` key and
-    initialisation); everything else is ``nn.Conv2d.forward``."""
-
-    def _native(self, x):
-        return (x.is_cuda and x.dim() == 4 and self.kernel_size == (3, 3) and self.padding == (1, 1) and self.dilation == (1, 1)
-                and self.stride == (2, 2) and self.groups == 1 and self.padding_mode == "zeros" and self.bias is None
-                and self.in_channels <= 3 and self.out_channels <= 32 and int(x.shape[1]) == self.in_channels)
-
-    def forward(self, x):
-        if not self._native(x):
-            return super(StemConv3x3s2, self).forward(x)
-        w = self.weight
-        if torch.is_autocast_enabled():
-            x = x.to(torch.get_autocast_dtype("cuda"))
-        if x.dtype not in (torch.bfloat16, torch.float16) or w.dtype != torch.float32:
-            return super(StemConv3x3s2, self).forward(x)
-        with torch.autocast("cuda", enabled=False):
-            return _StemConv3x3s2.apply(x.contiguous(), w)
-
-
-def use_native_stem(model):
-    """Switch the image-side 3x3 / stride-2 convolutions of ``model`` (<= 3 input channels, <= 32 filters, no bias) to the
-    kernel-backed subclass (in place).  -> layers switched."""
-    n = 0
-    for m in model.modules():
-        if (type(m) is nn.Conv2d and m.kernel_size == (3, 3) and m.padding == (1, 1) and m.stride == (2, 2) and m.groups == 1
-                and m.dilation == (1, 1) and m.padding_mode == "zeros" and m.bias is None and m.in_channels <= 3
-                and m.out_channels <= 32):
-            m.__class__ = StemConv3x3s2
-            n += 1
-    return n

@@ -18,9 +18,9 @@ import torch
 import torch.nn as nn
 
 from ssds import _native as N
+from ssds.modeling.layers import kernel_conv as K
 
 STATS = {"units": 0, "depthwise": 0, "pointwise": 0, "slice_forward": 0, "slice_backward": 0, "join_forward": 0, "join_backward": 0}
-_HALF = (torch.bfloat16, torch.float16)
 
 # The longest chain of dependent fp32 additions a product of ssdk_pws_wgrad (= ssdk_pw_wgrad) passes through, the bar of
 # tests/test_gpu_shuffle_train.py: |dW - truth| <= D 2^-24 sum |dy| |x|.  Both kernels (pw_wgrad_kernel, pw_wgrad_tiled_kernel):
@@ -76,7 +76,7 @@ def _pad8(v):
 
 
 def _kernel_tensor(t):
-    return torch.is_tensor(t) and t.is_cuda and t.dim() == 4 and t.dtype in _HALF and t.is_contiguous()
+    return torch.is_tensor(t) and t.is_cuda and t.dim() == 4 and t.dtype in K.HALF and t.is_contiguous()
 
 
 def _describe(t):
@@ -105,14 +105,14 @@ def prepare_weights(w, dt):
 
 def pws_forward(x_ptr, x_stride, a, bias, y_ptr, y_stride, b, k, m, hw, code, dev, want_sums=False):
     """One ssdk_pws_forward call on raw pointers (a: the padded matrix tensor [M, lda]); -> sums [M, 2] or None."""
-    sums = ws = None
+    sums = ws = wp = None
     need = 0
     if want_sums:
         need = int(N.lib.ssdk_pws_stats_workspace_bytes(b, k, m, hw))
-        ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+        ws, wp = K.workspace(dev, need)
         sums = torch.empty((m, 2), device=dev, dtype=torch.float32)
     N.check(N.lib.ssdk_pws_forward(x_ptr, x_stride, a.data_ptr(), int(a.shape[1]), None if bias is None else bias.data_ptr(), y_ptr, y_stride,
-                                   None if sums is None else sums.data_ptr(), None if ws is None else (ws.data_ptr() + 15) & ~15, need,
+                                   None if sums is None else sums.data_ptr(), wp, need,
                                    b, k, m, hw, code, N.stream_ptr(dev)), "pws_forward")
     return sums
 
@@ -120,9 +120,9 @@ def pws_forward(x_ptr, x_stride, a, bias, y_ptr, y_stride, b, k, m, hw, code, de
 def pws_wgrad(gy, x_ptr, x_stride, b, cout, cin, hw, code, dev):
     """-> dW [Cout, Cin, 1, 1] fp32 of a 1x1 convolution whose input lies at ``x_ptr`` with images ``x_stride`` elements apart."""
     need = int(N.lib.ssdk_pws_wgrad_workspace_bytes(b, cout, cin, hw))
-    ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+    ws, wp = K.workspace(dev, need)
     gw32 = torch.empty((cout, cin, 1, 1), device=dev, dtype=torch.float32)
-    N.check(N.lib.ssdk_pws_wgrad(gy.data_ptr(), x_ptr, x_stride, gw32.data_ptr(), (ws.data_ptr() + 15) & ~15, need, b, cout, cin, hw, code,
+    N.check(N.lib.ssdk_pws_wgrad(gy.data_ptr(), x_ptr, x_stride, gw32.data_ptr(), wp, need, b, cout, cin, hw, code,
                                  N.stream_ptr(dev)), "pws_wgrad")
     return gw32
 
@@ -266,7 +266,7 @@ def _kernel_inputs(*tensors):
             return None
         if autocast:
             t = t.to(torch.get_autocast_dtype("cuda"))
-        if t.dtype not in _HALF or not t.is_contiguous() or t.numel() == 0 or (out and (t.dtype != out[0].dtype or t.device != out[0].device)):
+        if t.dtype not in K.HALF or not t.is_contiguous() or t.numel() == 0 or (out and (t.dtype != out[0].dtype or t.device != out[0].device)):
             return None
         out.append(t)
     return out
@@ -364,15 +364,11 @@ def use_native_shuffle(model):
     if not backbones:
         return model
     for bb in backbones:
+        STATS["depthwise"] += K.swap_layers(bb, DepthwiseConv2d, also=lambda m: m.groups > 1)
         for m in bb.modules():
             if isinstance(m, InvertedResidual) and not m.__dict__.get("native_shuffle", False):
                 m.native_shuffle = True
                 STATS["units"] += 1
-            elif (type(m) is nn.Conv2d and m.kernel_size == (3, 3) and m.padding == (1, 1) and m.dilation == (1, 1)
-                  and m.stride in ((1, 1), (2, 2)) and m.groups == m.in_channels == m.out_channels > 1 and m.bias is None
-                  and m.padding_mode == "zeros"):
-                m.__class__ = DepthwiseConv2d
-                STATS["depthwise"] += 1
             elif _dense_1x1(m) and not m.__dict__.get("_ssdk_any_width", False):
                 m._ssdk_any_width = True
                 STATS["pointwise"] += 1

@@ -9,8 +9,9 @@ A ``Pass`` swaps layers of the freshly built (CPU, fp32) model to their kernel-b
   * dense3 runs before conv3_extras, which then skips the extras dense3 took (no longer plain nn.Conv2d);
   * the detector families (FPN / BiFPN, YOLO, Shelf) are mutually exclusive, so one order convt, dense3, neck, cat serves all three.
 
-To add a kernel family: write its ``use_native_*`` in the layer module with a ``DEFAULT``, add ONE entry here at the place its
-order constraints allow, a row in docs/SWITCHES.md, and regenerate tests/golden/route_digest.json (the digest names what moved).
+To add a kernel family: write its ``use_native_*`` in the layer module with a ``DEFAULT`` (a kernel-backed ``nn.Conv2d`` goes on
+``layers/kernel_conv.KernelConv2d``, which says what the class has to declare), add ONE entry here at the place its order
+constraints allow, a row in docs/SWITCHES.md, and regenerate tests/golden/route_digest.json (the digest names what moved).
 docs/SWITCHES.md has every switch with the measurement behind its default; DESIGN.md section 6 describes the table."""
 import collections
 import os
