@@ -31,7 +31,8 @@ extern "C" {
  *                           this does not depend on the threshold).  At threshold t it is a true positive iff that IoU >= t and no
  *                           detection of lower index reaches t on the same box.  max_dets is ignored.  With T = 1 the keys, flags
  *                           and counts are the bits ssdk_map_match writes.
- *   SSDK_AP_RULE_COCO       the greedy rule of pycocotools' evaluateImg, without crowd / ignore regions and without area ranges.
+ *   SSDK_AP_RULE_COCO       the greedy rule of pycocotools' evaluateImg for one area range without ignore regions (crowd boxes,
+ *                           area ranges, maxDets per category and recall: ssdk_cocoeval.h).
  *                           The caller passes each image's detections in descending score order.  Only the first max_dets valid
  *                           detections of an image (score > conf_threshold, 0 <= class < num_classes) count; the others get the
  *                           sentinel key like padding.  Per class and threshold independently the class's detections are walked in

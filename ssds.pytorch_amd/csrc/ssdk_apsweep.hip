@@ -272,26 +272,6 @@ __global__ __launch_bounds__(kMapThreads) void apsweep_coco_kernel(const SweepPa
   }
 }
 
-// how many of the 101 recall points r_k = k * 0.01 (r_100 = 1.0: numpy.linspace(0, 1, 101)) are <= x, compared in fp64
-__device__ __forceinline__ int coco_points_le(double x) {
-  int k = (int)(x * 100.0) + 2;
-  if (k > 100) k = 100;
-  while (k >= 0 && (k == 100 ? 1.0 : (double)k * 0.01) > x) --k;
-  return k + 1;
-}
-
-// 101-point interpolation as a sum over the true positives: the k-th one is the first rank whose recall is k / npos, so it answers
-// the recall points in ((k - 1) / npos, k / npos]; the first also answers r_0 = 0, whose envelope value is the same (precision is 0
-// before the first true positive).  The sum is divided by 101 afterwards.
-struct MapCocoWeight {
-  double dnp;
-  __device__ __forceinline__ double operator()(long long tpj) const {
-    const int hi = coco_points_le((double)tpj / dnp);
-    const int lo = tpj == 1 ? 0 : coco_points_le((double)(tpj - 1) / dnp);
-    return (double)(hi - lo);
-  }
-};
-
 // records sorted by key; seg[c] .. seg[c+1] is class c.  ap[t * C + c] = NaN when the class has no ground truth, 0 when it has no
 // detections.
 __global__ __launch_bounds__(64) void apsweep_ap_kernel(const int* mask, const long long* seg, const int* npos, int C, int rule,

@@ -161,6 +161,7 @@ _HEADERS = (
     ("ssdk_shuffletrain.h", {}),  # the ShuffleNetV2 TRAINING step: 1x1 on channel slices of any width, the interleaving join
     ("ssdk_densetrain.h", {}),  # the DenseNet dense-block TRAINING step on one buffer: place + sums, 1x1 with norm1 on load, norm1 backward
     ("ssdk_apsweep.h", {}),  # average precision over a sweep of IoU thresholds (AP@[.50:.95]): the reference's rule or the COCO rule
+    ("ssdk_cocoeval.h", {}),  # the COCO detection summary: area ranges, crowd boxes, maxDets per image and category, recall
 )
 # the library first: without it nothing below matters, and its message says how to build it -- no header error may mask it
 if not os.path.exists(LIB_PATH):
@@ -182,9 +183,9 @@ _K = _ABI.constants
 
 ABI_VERSION = _K["SSDK_VERSION"]  # a library of an older version is refused by _load
 (EXPORTS, CONVT_EXPORTS, CAT_EXPORTS, DKRES_EXPORTS, DCONV_EXPORTS, DENSE_EXPORTS, SHUFFLE_EXPORTS, CATTRAIN_EXPORTS,
- CONVTTRAIN_EXPORTS, SHUFFLETRAIN_EXPORTS, DENSETRAIN_EXPORTS, APSWEEP_EXPORTS) = (tuple(_h.functions) for _h in _PARSED)
+ CONVTTRAIN_EXPORTS, SHUFFLETRAIN_EXPORTS, DENSETRAIN_EXPORTS, APSWEEP_EXPORTS, COCOEVAL_EXPORTS) = (tuple(_h.functions) for _h in _PARSED)
 (_, CONVT_HEADER_PATH, CAT_HEADER_PATH, DKRES_HEADER_PATH, DCONV_HEADER_PATH, DENSE_HEADER_PATH, SHUFFLE_HEADER_PATH, CATTRAIN_HEADER_PATH,
- CONVTTRAIN_HEADER_PATH, SHUFFLETRAIN_HEADER_PATH, DENSETRAIN_HEADER_PATH, APSWEEP_HEADER_PATH) = _PATHS
+ CONVTTRAIN_HEADER_PATH, SHUFFLETRAIN_HEADER_PATH, DENSETRAIN_HEADER_PATH, APSWEEP_HEADER_PATH, COCOEVAL_HEADER_PATH) = _PATHS
 
 MAX_LEVELS, MAX_ANCHORS, MAX_TOPN, MAX_NDET, MAX_NMS_N, MAX_GT = (
     _K["SSDK_MAX_" + n] for n in ("LEVELS", "ANCHORS", "TOPN", "NDET", "NMS_N", "GT"))
@@ -234,6 +235,8 @@ SHUFFLE_CHUNK = _K["SSDK_SHUFFLE_CHUNK"]  # weight images and vectors are zero-p
 SPP_TRAIN_MAX_SIDE = _K["SSDK_SPP_TRAIN_MAX_SIDE"]  # the largest H / W ssdk_spp_train_* stage in LDS
 APSWEEP_MAX_T = _K["SSDK_APSWEEP_MAX_T"]  # IoU thresholds per ssdk_apsweep_match launch (include/ssdk_apsweep.h)
 AP_RULE = {"reference": _K["SSDK_AP_RULE_REFERENCE"], "coco": _K["SSDK_AP_RULE_COCO"]}
+# IoU thresholds, area ranges and maxDets values per ssdk_cocoeval_* call (include/ssdk_cocoeval.h)
+COCOEVAL_MAX_T, COCOEVAL_MAX_A, COCOEVAL_MAX_M = (_K["SSDK_COCOEVAL_MAX_" + n] for n in "TAM")
 
 
 def _load():

@@ -138,7 +138,8 @@ def sample_batch(rng, shapes, boxes, preproc, image_size, training, max_gt=None)
 
     -> (descs [B] of DESC_DTYPE with src_offset 0, targets [B, maxG, 5] float32, info); info holds per image ``option``
     (0 no crop, k threshold CROP_THRESHOLDS[k-1], -1 left uncropped after CROP_ROUNDS rounds), ``round``, the kept boxes
-    ``keep`` [B, G] (columns = the order of ``boxes[i]``), the colour parameters, and ``dropped`` (boxes cut by max_gt)."""
+    ``keep`` [B, G] (columns = the order of ``boxes[i]``), ``rows`` (per image: which of ``boxes[i]`` fill the rows of its targets),
+    the colour parameters, and ``dropped`` (boxes cut by max_gt)."""
     shapes = np.asarray(shapes, np.int64).reshape(-1, 2)
     B = shapes.shape[0]
     if len(boxes) != B:
@@ -207,22 +208,27 @@ def sample_batch(rng, shapes, boxes, preproc, image_size, training, max_gt=None)
         if G < 1:
             raise ValueError("max_gt must be at least 1")
     targets = np.full((B, G, 5), -1.0, np.float32)
+    which = []
     for i in range(B):
-        rows = xywh[i, keep[i]]
+        rows, src = xywh[i, keep[i]], np.nonzero(keep[i])[0]
         if len(rows) > G:  # only with max_gt: keep the largest by area, in their original order
             dropped += len(rows) - G
-            rows = rows[np.sort(np.argsort(-(rows[:, 2] * rows[:, 3]), kind="stable")[:G])]
+            largest = np.sort(np.argsort(-(rows[:, 2] * rows[:, 3]), kind="stable")[:G])
+            rows, src = rows[largest], src[largest]
         targets[i, :len(rows)] = rows
-    info.update(keep=keep, dropped=dropped)
+        which.append(src)
+    info.update(keep=keep, dropped=dropped, rows=which)
     return descs, targets, info
 
 
 class PackedDetectionSource(object):
     """Shards ``*.npz`` under ``path`` (tools/pack_dataset.py): ``pixels`` uint8 flat (HWC RGB images back to back),
     ``offsets`` [N] first byte of each image, ``shapes`` [N, 2] (height, width), ``boxes`` [M, 5] = (l, t, r, b, label >= 0)
-    in source pixels, ``box_offsets`` [N + 1].  Plain arrays: nothing is unpickled."""
+    in source pixels, ``box_offsets`` [N + 1].  Optional: ``box_crowd`` [M] int32 (non-zero = crowd region) and ``box_area`` [M]
+    float32 (source pixels), for the COCO summary of the eval phase.  Plain arrays: nothing is unpickled."""
 
     KEYS = ("pixels", "offsets", "shapes", "boxes", "box_offsets")
+    OPTIONAL = ("box_crowd", "box_area")
 
     def __init__(self, path):
         files = sorted(glob.glob(os.path.join(path, "*.npz")))
@@ -235,7 +241,12 @@ class PackedDetectionSource(object):
                 if missing:
                     raise ValueError("{}: missing arrays {}".format(f, missing))
                 s = {k: z[k] for k in self.KEYS}
+                extra = {k: z[k] for k in self.OPTIONAL if k in z.files}
             check_shard(f, **s)
+            for k, v in extra.items():
+                if v.shape != (len(s["boxes"]),):
+                    raise ValueError("{}: {} has shape {}, one value per box expected".format(f, k, v.shape))
+            s.update(extra)
             self.shards.append(s)
             starts.append(starts[-1] + len(s["shapes"]))
         self.starts = np.asarray(starts, np.int64)
@@ -266,6 +277,18 @@ class PackedDetectionSource(object):
     def boxes(self, i):
         s, j = self._locate(i)
         return s["boxes"][int(s["box_offsets"][j]):int(s["box_offsets"][j + 1])]
+
+    def _per_box(self, key, i):
+        s, j = self._locate(i)
+        return s[key][int(s["box_offsets"][j]):int(s["box_offsets"][j + 1])] if key in s else None
+
+    def crowd(self, i):
+        """[n_i] int32 crowd flags of image i's boxes, or None if its shard holds no ``box_crowd``."""
+        return self._per_box("box_crowd", i)
+
+    def area(self, i):
+        """[n_i] float32 annotation areas of image i's boxes (source pixels), or None if its shard holds no ``box_area``."""
+        return self._per_box("box_area", i)
 
 
 def check_shard(name, pixels, offsets, shapes, boxes, box_offsets):
@@ -307,15 +330,19 @@ class AugmentedLoader(object):
     consumer, which waits on an event.  Iterating starts the next epoch (``set_epoch`` chooses one).  ``max_gt``: None
     follows the reference's contract (maxG varies per batch); an integer pads every batch to that many rows
     (GraphedTrainStep's static tensors) and counts the boxes it had to drop in ``dropped``.  ``workers``: 1 stages in a worker
-    thread, 0 in the consumer's thread (same batches: every batch has its own generator)."""
+    thread, 0 in the consumer's thread (same batches: every batch has its own generator).  ``eval_extras`` (eval only): batches
+    are (images, targets, extras) with extras = dict(crowd [B,maxG] int32, area [B,maxG] float32 in source pixels, area_scale [B]
+    float32 = source pixels per network pixel) on ``device`` -- what ``CocoSummary`` takes next to the targets."""
 
     SLOTS = 3  # staging buffers: the batch whose kernel may still run, the one launched ahead, the one being packed
 
     def __init__(self, source, dataset_cfg, batch_size, device, dtype=None, training=True, seed=1234, rank=0, world_size=1,
-                 max_gt=None, image_size=None, workers=1):
+                 max_gt=None, image_size=None, workers=1, eval_extras=False):
         self.source, self.cfg, self.batch_size, self.device = source, dataset_cfg, int(batch_size), device
         self.dtype, self.training, self.seed, self.rank, self.world_size = dtype, bool(training), int(seed), int(rank), int(world_size)
-        self.max_gt, self.workers = max_gt, int(workers)
+        self.max_gt, self.workers, self.eval_extras = max_gt, int(workers), bool(eval_extras)
+        if self.eval_extras and self.training:
+            raise ValueError("AugmentedLoader: eval_extras describes the un-augmented boxes of an eval batch (training=False)")
         self.image_size = tuple(int(v) for v in (image_size if image_size is not None else dataset_cfg["IMAGE_SIZE"]))
         self.preproc = dataset_cfg["PREPROC"]
         self.mean, self.std = vec3(self.preproc["MEAN"]), vec3(self.preproc["STD"])
@@ -344,6 +371,26 @@ class AugmentedLoader(object):
         descs["src_offset"] = np.concatenate([[0], np.cumsum(size)[:-1]])
         return descs, targets, info, int(size.sum())
 
+    def extras(self, indices, targets, info):
+        """Host half of ``eval_extras``: numpy crowd / area [B, maxG] along the rows of ``targets`` (0 on padding rows; the source
+        box area where the shard holds no ``box_area``, 0 where it holds no ``box_crowd``) and area_scale [B]."""
+        B, G = targets.shape[0], targets.shape[1]
+        crowd, area, scale = np.zeros((B, G), np.int32), np.zeros((B, G), np.float32), np.zeros(B, np.float32)
+        has = lambda f: getattr(self.source, f, None) is not None  # noqa: E731
+        for b, i in enumerate(indices):
+            rows = info["rows"][b]
+            h, w = self.source.shape(int(i))
+            scale[b] = (w / float(self.image_size[1])) * (h / float(self.image_size[0]))
+            c = self.source.crowd(int(i)) if has("crowd") else None
+            a = self.source.area(int(i)) if has("area") else None
+            if a is None:
+                bx = np.asarray(self.source.boxes(int(i)), np.float32).reshape(-1, 5)
+                a = (bx[:, 2] - bx[:, 0]) * (bx[:, 3] - bx[:, 1])
+            area[b, :len(rows)] = np.asarray(a, np.float32)[rows]
+            if c is not None:
+                crowd[b, :len(rows)] = np.asarray(c, np.int32)[rows]
+        return dict(crowd=crowd, area=area, area_scale=scale)
+
     # ---- staging (a worker thread) and launch (the consumer's thread) ------------------------------------------------
     def _prepare(self, k, epoch, batch_index, indices):
         """Worker thread: sample the descriptors and pack the batch's images into the slot's pinned buffers."""
@@ -369,7 +416,8 @@ class AugmentedLoader(object):
         if t_host is None:
             t_host = s["targets"][targets.shape] = torch.empty(targets.shape, dtype=torch.float32, pin_memory=True)
         t_host.numpy()[...] = targets
-        return dict(slot=s, B=B, nbytes=nbytes, targets=t_host, dropped=info["dropped"])
+        extras = self.extras(indices, targets, info) if self.eval_extras else None
+        return dict(slot=s, B=B, nbytes=nbytes, targets=t_host, dropped=info["dropped"], extras=extras)
 
     def _launch(self, prep):
         """Consumer's thread: upload and kernel on the side stream, an event behind them."""
@@ -390,9 +438,12 @@ class AugmentedLoader(object):
             targets = prep["targets"].to(self.device, non_blocking=True)
             images = torch.empty((B, 3) + self.image_size, dtype=dtype, device=self.device)
             augment_into(images, s["dev"], nbytes, s["descs"].numpy(), B, self.mean, self.std, s["ws"])
+            extras = None
+            if prep["extras"] is not None:  # (a few hundred bytes: from pageable memory, the copy is done when .to returns)
+                extras = {k: torch.from_numpy(v).to(self.device) for k, v in prep["extras"].items()}
             s["event"] = torch.cuda.Event()
             s["event"].record(self._stream)
-        return images, targets, s["event"]
+        return images, targets, s["event"], extras
 
     def __iter__(self):
         import torch
@@ -411,7 +462,7 @@ class AugmentedLoader(object):
         staged = {b: self._pool.submit(self._prepare, b, epoch, b, batches[b]) for b in range(min(2, n))}
         nxt = self._launch(staged.pop(0).result())
         for b in range(n):
-            images, targets, event = nxt
+            images, targets, event, extras = nxt
             if b + 1 < n:
                 nxt = self._launch(staged.pop(b + 1).result())
             if b + 2 < n:
@@ -420,6 +471,11 @@ class AugmentedLoader(object):
             cur.wait_event(event)
             images.record_stream(cur)  # allocated on the side stream, consumed on this one
             targets.record_stream(cur)
+            if extras is not None:
+                for v in extras.values():
+                    v.record_stream(cur)
+                yield images, targets, extras
+                continue
             yield images, targets
         if self.rank == 0 and self.max_gt is not None:
             print("AugmentedLoader: epoch {}: {} boxes dropped by max_gt = {}".format(epoch, self.dropped, self.max_gt))

@@ -276,12 +276,17 @@ def eval_anchor_based_epoch(model, data_loader, decoder, anchors, num_classes, d
 
     ``metrics``: a sequence of metric objects (``MeanAveragePrecision``, ``AveragePrecisionSweep``) instead of the default
     one: each is fed every batch, merged over the ranks at the end when a process group of more than one rank is initialised
-    (every rank then holds the result of the whole data set), and the list of their ``get_results()`` is returned."""
+    (every rank then holds the result of the whole data set), and the list of their ``get_results()`` is returned.
+
+    A loader may yield (images, targets, extras) with extras = dict(crowd, area, area_scale) (``AugmentedLoader(eval_extras=True)``):
+    a metric that declares ``takes_extras`` (``CocoSummary``) gets them as keywords, the others get the same ``targets`` as ever."""
     from ssds.core.evaluation_metrics import MeanAveragePrecision
 
     model.eval()
     fed = [MeanAveragePrecision(num_classes, decoder.conf_threshold, decoder.nms_threshold)] if metrics is None else list(metrics)
-    for images, targets in data_loader:
+    for batch in data_loader:
+        images, targets = batch[0], batch[1]
+        extras = batch[2] if len(batch) > 2 and batch[2] is not None else {}
         if images.device != device:
             images, targets = images.to(device), targets.to(device)
         targets = targets.float().clone()
@@ -289,7 +294,10 @@ def eval_anchor_based_epoch(model, data_loader, decoder, anchors, num_classes, d
         detections = decoder(loc, conf, anchors)
         targets[:, :, 2:4] = targets[:, :, :2] + targets[:, :, 2:4]  # xywh -> ltrb (:175)
         for metric in fed:
-            metric(detections, targets)
+            if getattr(metric, "takes_extras", False):
+                metric(detections, targets, **extras)
+            else:
+                metric(detections, targets)
     if metrics is None:
         return fed[0].get_results()
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:

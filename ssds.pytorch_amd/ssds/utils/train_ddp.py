@@ -70,9 +70,12 @@ class _CountImages(object):
         self.loader, self.images = loader, 0
 
     def __iter__(self):
-        for images, targets in self.loader:
-            self.images += int(images.shape[0])
-            yield images, targets
+        for batch in self.loader:  # (images, targets) or (images, targets, extras)
+            self.images += int(batch[0].shape[0])
+            yield batch
+
+
+COCO_SUMMARY_KEYS = ("APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")  # what eval_model adds from CocoSummary
 
 
 def _json_number(v):
@@ -163,20 +166,22 @@ class Solver(object):
 
             world = dist.get_world_size() if dist.is_initialized() else 1
             return AugmentedLoader(PackedDetectionSource(self.data), self.cfg.DATASET, self.cfg.TEST.BATCH_SIZE, self.device, dtype=dtype,
-                                   training=False, seed=1234, rank=rank, world_size=world, image_size=self.cfg.MODEL.IMAGE_SIZE)
+                                   training=False, seed=1234, rank=rank, world_size=world, image_size=self.cfg.MODEL.IMAGE_SIZE,
+                                   eval_extras=True)
         return SyntheticDetectionLoader(self.cfg.TEST.BATCH_SIZE, self.cfg.MODEL.IMAGE_SIZE, self.cfg.MODEL.NUM_CLASSES,
                                         self.steps_per_epoch, self.device, seed=1234 + rank, dtype=dtype)
 
     def eval_model(self, data=None, dtype=torch.bfloat16):
         """The reference's ``eval_model`` (train.py:161-209) on all ranks: every checkpoint ``select_checkpoints`` picks is
         evaluated with the reference's metric (``MeanAveragePrecision`` at the decoder's NMS threshold -- the reference's
-        choice, quirk included) and the COCO sweep (AP@[.50:.95]).  Rank 0 prints one line per checkpoint and appends it as
+        choice, quirk included), the COCO sweep (AP@[.50:.95]) and the COCO summary (``CocoSummary``: AP by area, AR by maxDets and
+        by area, crowd regions ignored -- crowd flags and annotation areas come from the shards where they hold them).  Rank 0 prints one line per checkpoint and appends it as
         JSON to ``EXP_DIR/eval_results.jsonl``; -> the list of those records (on every rank).
 
         Every checkpoint gets a FRESH, unrouted model (``create_model``, load, ``.eval().to(device, dtype)`` as ``SSDDetector``
         does): the recorded plan of a model keeps the weight packs it was recorded with, so loading a second checkpoint into a
         model that has already run would evaluate the first one's weights."""
-        from ssds.core.evaluation_metrics import AveragePrecisionSweep, MeanAveragePrecision
+        from ssds.core.evaluation_metrics import AveragePrecisionSweep, CocoSummary, MeanAveragePrecision
         from ssds.pipeline.pipeline_anchor_ddp import eval_anchor_based_epoch
 
         cfg = self.cfg
@@ -198,13 +203,13 @@ class Solver(object):
             model.eval().to(self.device, dtype)
             anchors = model_builder.create_anchors(cfg.MODEL, model, cfg.MODEL.IMAGE_SIZE)
             metrics = [MeanAveragePrecision(classes, decoder.conf_threshold, decoder.nms_threshold),
-                       AveragePrecisionSweep(classes, decoder.conf_threshold)]
+                       AveragePrecisionSweep(classes, decoder.conf_threshold), CocoSummary(classes, decoder.conf_threshold)]
             loader = _CountImages(self.eval_loader(dtype))
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
             start = time.time()
-            (ref_map, _), (ap, detail) = eval_anchor_based_epoch(model, loader, decoder, anchors, classes, self.device,
-                                                                 metrics=metrics)
+            (ref_map, _), (ap, detail), (_, coco) = eval_anchor_based_epoch(model, loader, decoder, anchors, classes, self.device,
+                                                                            metrics=metrics)
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
             seconds = time.time() - start
@@ -216,12 +221,14 @@ class Solver(object):
             record = {"epoch": int(epoch), "checkpoint": path, "mAP_reference": _json_number(float(ref_map)),
                       "AP": _json_number(float(ap)), "AP50": _json_number(per_iou.get(0.5)), "AP75": _json_number(per_iou.get(0.75)),
                       "images": int(images), "seconds": round(seconds, 3)}
+            for key in COCO_SUMMARY_KEYS:  # AP / AP50 / AP75 stay those of the sweep
+                record[key] = _json_number(float(coco["summary"][key]))
             records.append(record)
             if first_rank:
                 show = lambda v: "nan" if v is None else "{:.4f}".format(v)  # noqa: E731
-                print("Eval: epoch {} | mAP(reference) {} | AP@[.50:.95] {} | AP50 {} | AP75 {} | {} images | {:.1f}s".format(
+                print("Eval: epoch {} | mAP(reference) {} | AP@[.50:.95] {} | AP50 {} | AP75 {} | {} | {} images | {:.1f}s".format(
                     epoch, show(record["mAP_reference"]), show(record["AP"]), show(record["AP50"]), show(record["AP75"]),
-                    record["images"], seconds))
+                    " | ".join("{} {}".format(key, show(record[key])) for key in COCO_SUMMARY_KEYS), record["images"], seconds))
                 os.makedirs(cfg.EXP_DIR, exist_ok=True)
                 with open(os.path.join(cfg.EXP_DIR, "eval_results.jsonl"), "a") as f:
                     f.write(json.dumps(record) + "\n")

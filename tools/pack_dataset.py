@@ -1,10 +1,13 @@
 #!/usr/bin/env python
 """Write shards for ``ssds.dataset.augment.PackedDetectionSource``: ``*.npz`` holding ``pixels`` (uint8, flat: HWC RGB
 images back to back), ``offsets`` [N], ``shapes`` [N, 2] (height, width), ``boxes`` [M, 5] = (l, t, r, b, label >= 0) in
-source pixels and ``box_offsets`` [N + 1] -- the layout ``ssdk_augment`` takes, no pickled objects.
+source pixels and ``box_offsets`` [N + 1] -- the layout ``ssdk_augment`` takes, no pickled objects.  Optional, for the COCO
+summary of the eval phase: ``box_crowd`` [M] int32 (non-zero = crowd region) and ``box_area`` [M] float32 (the annotation's area in
+source pixels, e.g. of its mask), in the order of ``boxes``.
 
     from tools.pack_dataset import write_shards
     write_shards(out_dir, images, boxes, per_shard=256)        # images: HxWx3 uint8 arrays, boxes: [n_i, 5] arrays
+    write_shards(out_dir, images, boxes, crowd=c, area=a)      # c, a: [n_i] arrays per image (either may be left out)
 
     python tools/pack_dataset.py --synthetic 256 --out DIR     # a seeded toy set: filled rectangles on a gradient,
                                                                # the rectangles being the boxes
@@ -21,12 +24,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ssds.pytorch_amd"))
 
 
-def write_shards(out_dir, images, boxes, per_shard=256, prefix="shard"):
-    """-> the shard paths, in order."""
+def write_shards(out_dir, images, boxes, per_shard=256, prefix="shard", crowd=None, area=None):
+    """-> the shard paths, in order.  ``crowd`` / ``area``: per image an array [n_i] in the order of its boxes, written as
+    ``box_crowd`` / ``box_area``; None: the shard holds no such array."""
     from ssds.dataset.augment import check_shard
 
     if len(images) != len(boxes):
         raise ValueError("{} images but {} box arrays".format(len(images), len(boxes)))
+    for name, extra in (("crowd", crowd), ("area", area)):
+        if extra is not None and (len(extra) != len(boxes) or any(np.asarray(e).reshape(-1).shape[0] != np.asarray(b).reshape(-1, 5).shape[0]
+                                                                   for e, b in zip(extra, boxes))):
+            raise ValueError("{}: one value per box of every image".format(name))
     os.makedirs(out_dir, exist_ok=True)
     paths = []
     for k, lo in enumerate(range(0, len(images), per_shard)):
@@ -43,6 +51,9 @@ def write_shards(out_dir, images, boxes, per_shard=256, prefix="shard"):
                      box_offsets=np.concatenate([[0], np.cumsum([len(b) for b in bxs])]).astype(np.int64))
         path = os.path.join(out_dir, "{}_{:05d}.npz".format(prefix, k))
         check_shard(path, **shard)
+        for key, extra, dtype in (("box_crowd", crowd, np.int32), ("box_area", area, np.float32)):
+            if extra is not None:
+                shard[key] = np.concatenate([np.asarray(e, dtype).reshape(-1) for e in extra[lo:lo + per_shard]] + [np.zeros(0, dtype)])
         np.savez(path, **shard)
         paths.append(path)
     return paths
