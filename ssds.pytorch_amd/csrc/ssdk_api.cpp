@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "ssdk_common.h"
+#include "../../include/ssdk_variant.h"
 
 namespace ssdk {
 
@@ -20,8 +21,62 @@ void set_error(const char* fmt, ...) {
 
 static thread_local const char* g_last_kernel = "";
 
+// ssdk_last_variant(): what the launcher noted (plain integers, no formatting on the launch path) and the text made from it on read
+struct VariantNote {
+  int kind, v[8];
+  bool fresh;
+};
+static thread_local VariantNote g_variant = {VAR_NONE, {0, 0, 0, 0, 0, 0, 0, 0}, false};
+static thread_local char g_variant_text[160] = "";
+
+void note_variant(int kind, int a, int b, int c, int d, int e, int f, int g, int h) {
+  VariantNote& n = g_variant;
+  n.kind = kind;
+  n.v[0] = a, n.v[1] = b, n.v[2] = c, n.v[3] = d, n.v[4] = e, n.v[5] = f, n.v[6] = g, n.v[7] = h;
+  n.fresh = true;
+}
+
+// "<instance> | <sizes of this launch>": the part before " | " names the template instance and the branch of the launcher (what a
+// table of instances lists), the part behind it the numbers that change with the layer's size
+static const char* variant_text() {
+  const VariantNote& n = g_variant;
+  const int* v = n.v;
+  char* t = g_variant_text;
+  const size_t cap = sizeof(g_variant_text);
+  switch (n.kind) {
+    case VAR_GEMM:  // tile width, n64, resv, splits
+      snprintf(t, cap, "gemm bn=%d n64=%d resv=%d %s | splits=%d", v[0], v[1], v[2], v[3] > 1 ? "split" : "unsplit", v[3]);
+      break;
+    case VAR_WAVE: snprintf(t, cap, "wave %s | splits=%d", v[0] > 1 ? "split" : "unsplit", v[0]); break;
+    case VAR_HALO: {  // form (1 persistent), imgs, th, tw, ksplits, vec_nchw, nchw; vec_nchw is read by the first form's NCHW stores only
+      char vec[16] = "";
+      if (!v[0] && v[6]) snprintf(vec, sizeof(vec), " vec_nchw=%d", v[5]);
+      snprintf(t, cap, "halo %s %s %s%s | patch=%dx%dx%d ksplits=%d", v[0] ? "persistent" : "first", v[6] ? "nchw" : "nhwc",
+               v[4] > 1 ? "split" : "unsplit", vec, v[1], v[2], v[3], v[4]);
+      break;
+    }
+    case VAR_SHORT:  // cs, layout (0 nhwc, 1 nchw, 2 nchw-wide), nsplit, tpw
+      snprintf(t, cap, "short cs=%d %s | nsplit=%d tpw=%d", v[0], v[1] == 2 ? "nchw-wide" : (v[1] == 1 ? "nchw" : "nhwc"), v[2], v[3]);
+      break;
+    case VAR_SMALLMAP:  // cs, mfr, taps, packed, na, stride, kw
+      snprintf(t, cap, "smallmap mfr=%d taps=%d packed=%d na=%d stride=%d kw=%d | cs=%d", v[1], v[2], v[3], v[4], v[5], v[6], v[0]);
+      break;
+    case VAR_PWFLOW: snprintf(t, cap, "pwflow ks=%d nf=%d | slices=%d", v[0], v[1], v[2]); break;
+    case VAR_GEMMP:  // grid, tq, tr
+      snprintf(t, cap, "gemmp %s | grid=%d tq=%d tr=%d", v[2] ? "remainder" : "even", v[0], v[1], v[2]);
+      break;
+    case VAR_GEMM256: snprintf(t, cap, "gemm256 | tiles=%d", v[0]); break;
+    case VAR_FIRST: snprintf(t, cap, "first cout=%d %s", v[0], v[1] ? "nhwc" : "nchw"); break;
+    case VAR_DW: snprintf(t, cap, "dw stride=%d", v[0]); break;
+    default: t[0] = 0; break;
+  }
+  return t;
+}
+
 int check_launch(const char* what) {
   g_last_kernel = what;
+  if (!g_variant.fresh) g_variant.kind = VAR_NONE;
+  g_variant.fresh = false;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("%s: %s", what, hipGetErrorString(e));
@@ -56,6 +111,7 @@ extern "C" int ssdk_abi_check(int header_version, size_t sizeof_op) {
 }
 extern "C" const char* ssdk_last_error(void) { return ssdk::g_err; }
 extern "C" const char* ssdk_last_kernel(void) { return ssdk::g_last_kernel; }
+extern "C" const char* ssdk_last_variant(void) { return ssdk::variant_text(); }
 
 extern "C" int ssdk_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes, char* arch, int arch_len) {
   int dev = 0;

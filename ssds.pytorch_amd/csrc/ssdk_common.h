@@ -21,6 +21,13 @@ constexpr int kWave = 64;
 // ---- host-side error plumbing (ssdk_api.cpp) -------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// The template instance behind the name check_launch() records, for ssdk_last_variant() (include/ssdk_variant.h): the launcher
+// stores plain integers right before its check_launch(), the text is made when somebody asks.  A launch that notes nothing
+// reports "" -- check_launch() drops a note that is not fresh.
+enum {
+  VAR_NONE = 0, VAR_GEMM, VAR_WAVE, VAR_HALO, VAR_SHORT, VAR_SMALLMAP, VAR_PWFLOW, VAR_GEMMP, VAR_GEMM256, VAR_FIRST, VAR_DW
+};
+void note_variant(int kind, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0, int f = 0, int g = 0, int h = 0);
 void lds_poison(hipStream_t stream);  // ssdk_debug.hip: no-op unless SSDK_LDS_POISON=1
 
 // ---- order-preserving float <-> u32 (total order on non-NaN floats) ---------------------------

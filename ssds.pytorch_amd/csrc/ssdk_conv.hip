@@ -996,6 +996,7 @@ static int launch_gemm256(const ConvParams& p, hipStream_t stream) {
   }
   const unsigned tiles = (unsigned)((p.M + G2_BM - 1) / G2_BM) * (unsigned)((p.Cout + G2_BN - 1) / G2_BN);
   hipLaunchKernelGGL((conv_gemm256_kernel<DT>), dim3(tiles), dim3(G2_THREADS), G2_LDS, stream, p);
+  note_variant(VAR_GEMM256, (int)tiles);
   return check_launch("conv_gemm256_kernel");
 }
 
@@ -1023,6 +1024,7 @@ static int launch_gemm(const ConvParams& p, hipStream_t stream) {
   else if (p.Cout > 16) SSDK_GEMM(4, 1, 2, 2, 1);
   else SSDK_GEMM(4, 1, 2, 1, 1);
 #undef SSDK_GEMM
+  note_variant(VAR_GEMM, n64 ? 64 : gemm_bn(p.Cout), n64 ? 1 : 0, (gz == 1 && resv) ? 1 : 0, (int)gz);
   return check_launch("conv_gemm_kernel");
 }
 
@@ -1146,6 +1148,7 @@ extern "C" int ssdk_conv(const ssdk_conv_desc* d, void* workspace, size_t worksp
       if (d->stride == 1) hipLaunchKernelGGL((dwconv3x3_kernel<SSDK_F16, 1>), dim3(grid), dim3(256), 0, stream, p);
       else hipLaunchKernelGGL((dwconv3x3_kernel<SSDK_F16, 2>), dim3(grid), dim3(256), 0, stream, p);
     }
+    note_variant(VAR_DW, d->stride);
     return check_launch("dwconv3x3_kernel");
   }
   if (d->groups != 1) {  // grouped 3x3 (RegNetX / ResNeXt bottlenecks): 16 channels per group on its own kernels, other widths on one
@@ -1191,6 +1194,7 @@ extern "C" int ssdk_conv(const ssdk_conv_desc* d, void* workspace, size_t worksp
       else SSDK_FIRST(SSDK_F16, 64);
     }
 #undef SSDK_FIRST
+    note_variant(VAR_FIRST, d->Cout, d->in_layout == LAYOUT_NHWC ? 1 : 0);
     return check_launch("conv_first_kernel");
   }
   if ((d->Cin % 8) || d->in_layout != LAYOUT_NHWC) {
@@ -1295,6 +1299,7 @@ extern "C" int ssdk_conv(const ssdk_conv_desc* d, void* workspace, size_t worksp
         hipLaunchKernelGGL((conv_wave_kernel<SSDK_BF16>), dim3((waves + 3) / 4), dim3(256), 0, stream, p, mt, ntl);
       else
         hipLaunchKernelGGL((conv_wave_kernel<SSDK_F16>), dim3((waves + 3) / 4), dim3(256), 0, stream, p, mt, ntl);
+      note_variant(VAR_WAVE, ws);
       return check_launch("conv_wave_kernel");
     }
   }

@@ -1017,6 +1017,7 @@ int launch_conv3x3_halo(const ConvParams& p, int dtype, hipStream_t stream, bool
         fprintf(stderr, "[h3p dbg] store acknowledgements after the last tile: %lld\n", h[242] - h[(hp.tq + (hp.dbg_wg < hp.tr ? 1 : 0) - 1) * 8 + 6]);
       }
     }
+    note_variant(VAR_HALO, 1, hp.imgs, hp.th, hp.tw, hp.ksplits, hp.vec_nchw, nchw_out ? 1 : 0);
     return check_launch("conv3x3_halo_kernel");
   }
   if (dbg) {
@@ -1044,6 +1045,7 @@ int launch_conv3x3_halo(const ConvParams& p, int dtype, hipStream_t stream, bool
                 h[i * 4 + 3] - h[i * 4 + 2], (i < 63 && h[(i + 1) * 4]) ? h[(i + 1) * 4] - h[i * 4] : 0ll);
     }
   }
+  note_variant(VAR_HALO, 0, hp.imgs, hp.th, hp.tw, hp.ksplits, hp.vec_nchw, nchw_out ? 1 : 0);
   return check_launch("conv3x3_halo_kernel");
 }
 

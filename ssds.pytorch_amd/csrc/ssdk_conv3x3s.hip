@@ -456,6 +456,7 @@ int launch_conv3x3_short(const ConvParams& p, int dtype, hipStream_t stream) {
 #undef SSDK_S3A
 #undef SSDK_S3W
 #undef SSDK_S3
+  note_variant(VAR_SHORT, cs, nchw ? (wide ? 2 : 1) : 0, nsplit, sp.tpw);
   return 0;
 }
 

@@ -430,6 +430,7 @@ int launch_conv_gemmp(const ConvParams& p, int dtype, hipStream_t stream) {
                 h[i * 8 + 5] - h[i * 8 + 4], h[i * 8 + 6] - h[i * 8 + 5]);
     }
   }
+  note_variant(VAR_GEMMP, (int)grid, (int)gp.tq, (int)gp.tr);
   return check_launch("conv_gemmp_kernel");
 }
 

@@ -243,6 +243,7 @@ int launch_conv_pwflow(const ConvParams& p, int dtype, hipStream_t stream) {
 #undef SSDK_PWD
 #undef SSDK_PWK
 #undef SSDK_PW
+  note_variant(VAR_PWFLOW, ksi, nf, pp.slices);
   return 0;
 }
 

@@ -410,6 +410,11 @@ int launch_conv_smallmap(const ConvParams& p, int dtype, hipStream_t stream) {
 #undef SSDK_SM0
 #undef SSDK_SMK2
 #undef SSDK_SMS
+  {  // the template arguments SSDK_SM chose above: <CS, MFR, TAPS, PK, NA, S, KW>
+    const bool one = !s2 && P == 1, two = !s2 && !one && na == 2;
+    note_variant(VAR_SMALLMAP, cs, (s2 || one || two) ? 4 : mfr, one ? 1 : 9, (s2 || two || packed) ? 1 : 0, (s2 || two) ? 2 : 1, s2 ? 2 : 1,
+                 (two && kw == 2) ? 2 : 1);
+  }
   return 0;
 }
 

@@ -162,6 +162,7 @@ _HEADERS = (
     ("ssdk_densetrain.h", {}),  # the DenseNet dense-block TRAINING step on one buffer: place + sums, 1x1 with norm1 on load, norm1 backward
     ("ssdk_apsweep.h", {}),  # average precision over a sweep of IoU thresholds (AP@[.50:.95]): the reference's rule or the COCO rule
     ("ssdk_cocoeval.h", {}),  # the COCO detection summary: area ranges, crowd boxes, maxDets per image and category, recall
+    ("ssdk_variant.h", {}),  # ssdk_last_variant: the template instance behind ssdk_last_kernel's name (tests, tools)
 )
 # the library first: without it nothing below matters, and its message says how to build it -- no header error may mask it
 if not os.path.exists(LIB_PATH):
@@ -183,9 +184,9 @@ _K = _ABI.constants
 
 ABI_VERSION = _K["SSDK_VERSION"]  # a library of an older version is refused by _load
 (EXPORTS, CONVT_EXPORTS, CAT_EXPORTS, DKRES_EXPORTS, DCONV_EXPORTS, DENSE_EXPORTS, SHUFFLE_EXPORTS, CATTRAIN_EXPORTS,
- CONVTTRAIN_EXPORTS, SHUFFLETRAIN_EXPORTS, DENSETRAIN_EXPORTS, APSWEEP_EXPORTS, COCOEVAL_EXPORTS) = (tuple(_h.functions) for _h in _PARSED)
+ CONVTTRAIN_EXPORTS, SHUFFLETRAIN_EXPORTS, DENSETRAIN_EXPORTS, APSWEEP_EXPORTS, COCOEVAL_EXPORTS, VARIANT_EXPORTS) = (tuple(_h.functions) for _h in _PARSED)
 (_, CONVT_HEADER_PATH, CAT_HEADER_PATH, DKRES_HEADER_PATH, DCONV_HEADER_PATH, DENSE_HEADER_PATH, SHUFFLE_HEADER_PATH, CATTRAIN_HEADER_PATH,
- CONVTTRAIN_HEADER_PATH, SHUFFLETRAIN_HEADER_PATH, DENSETRAIN_HEADER_PATH, APSWEEP_HEADER_PATH, COCOEVAL_HEADER_PATH) = _PATHS
+ CONVTTRAIN_HEADER_PATH, SHUFFLETRAIN_HEADER_PATH, DENSETRAIN_HEADER_PATH, APSWEEP_HEADER_PATH, COCOEVAL_HEADER_PATH, VARIANT_HEADER_PATH) = _PATHS
 
 MAX_LEVELS, MAX_ANCHORS, MAX_TOPN, MAX_NDET, MAX_NMS_N, MAX_GT = (
     _K["SSDK_MAX_" + n] for n in ("LEVELS", "ANCHORS", "TOPN", "NDET", "NMS_N", "GT"))
@@ -378,6 +379,12 @@ def op_timings():
 def last_kernel():
     """Name of the kernel this thread launched last (which variant a layer was dispatched to)."""
     return lib.ssdk_last_kernel().decode()
+
+
+def last_variant():
+    """The template instance and launcher branch behind ``last_kernel()``'s name (include/ssdk_variant.h): "<instance> | <sizes>",
+    or "" for a kernel whose launcher notes none."""
+    return lib.ssdk_last_variant().decode()
 
 
 class SsdkError(RuntimeError):
